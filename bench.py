@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- bucketMul throughput on MI355X (driver contract: DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--group 32] [--streams 4] [--effort 0.25]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--group 32] [--streams 4] [--effort 0.25] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): Mistral-7B-FFN-shaped matrix 4096 x 11008, fp16 buckets, bucketMul at 25 % effort (the
 north-star operating point), plus an effort sweep 10..100 % in the full record.  One STEP = one pass of the hot path over one
@@ -11,31 +11,33 @@ HBM before the timed region.  The calls of a step are independent (as Wq|Wk|Wv o
 issued `--group` at a time through effort_bucketmul_group, ONE kernel launch per group.  The K steps of the job are independent
 too: they go through ONE context with effort_set_overlap(S) -- the library keeps up to S = `--streams` launches in flight on
 its own lanes -- and every step in flight multiplies its OWN 32 matrices (S x 32 distinct matrices, 11.8 GB: nothing a
-concurrent launch reads can come out of the 256 MB Infinity Cache on another launch's behalf).  The job is one hipGraph,
-repeated until the timed region is >= 50 ms; the host is not in the timed path (the reference's timeIt,
-helpers/timeit.swift:10-34, likewise enqueues everything and waits once).  After the timed replays EVERY output set the timed
-graph wrote is checked against the CPU oracle (S x 32 outputs).
+concurrent launch reads can come out of the 256 MB Infinity Cache on another launch's behalf).  The W warm-up steps and the K
+timed steps are one hipGraph each; the timed region is ONE replay of the K-step graph, exactly K steps; the host is not in the
+timed path (the reference's timeIt, helpers/timeit.swift:10-34, likewise enqueues everything and waits once).  Inputs are
+seeded: the same flags give the same inputs, run to run.
 
-What this file measures (the driver's one command): the headline, `roofline` (+ the in-run PMC traffic passes, `single_stream`),
-`cpu_baseline`, `by_group_size`, the effort sweep, the dense baselines, config 0/1's shape and config 3 (Q4), the decode
-scalars, a slim `timeit_protocol`.  Everything else round 5's bench carried -- by_streams, four_contexts, shared_matrices,
-shard_projection, the timeit variants, quality sweeps, the one-GPU layer_latency -- lives in tools/bench_extra.py (writes
-gpurun_out/bench_extra.json).
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, `--dump-outputs DIR` (the last
+step's 32 output vectors as DIR/out.npy, float32), the result line.  `--full` adds every other section after the headline:
+`roofline` (+ the in-run PMC traffic passes, `single_stream`), `by_group_size`, a slim `timeit_protocol`, the dense baselines,
+the effort sweep, config 0/1's shape and config 3 (Q4), the decode scalars, `cpu_baseline` + the check of EVERY output set the
+timed graph wrote against the CPU oracle (S x 32 outputs); at N > 1 the `multi_gpu` legs.  Everything else round 5's bench
+carried -- by_streams, four_contexts, shared_matrices, shard_projection, the timeit variants, quality sweeps, the one-GPU
+layer_latency -- lives in tools/bench_extra.py.
 
 value            = effective (dense-equivalent) GB/s = 2*inDim*outDim bytes per call / time per call, whole job over all ranks.
 tokens_per_s     = the reference's projection 1/(t_call * 4 * 32) (helpers/timeit.swift:26,33-34).
-roofline         = dominant kernel (bucket_mul_kernel: a whole group of calls in one launch).  achieved = algorithmic bytes the
+roofline (--full) = dominant kernel (bucket_mul_kernel: a whole group of calls in one launch).  achieved = algorithmic bytes the
                    timed region moved / the timed region; `single_stream` gives the same job with ONE launch in flight (launch
                    duration = timed region / launches, which is what `rocprofv3 --kernel-trace --stats` reports: profiles/).
-steps            = K as asked for (the driver's flag); `timed_steps` = K x repetitions is what the timed region really holds
-                   (`timed_region_ms`), `steps_requested` repeats K.
+steps            = K as asked for (the driver's flag) = `timed_steps`, what the timed region holds (`timed_region_ms`);
+ms_per_step      = the timed region / K.
 
 N > 1: `python bench.py --gpus N` STARTS ITS N RANKS ITSELF when no launcher did (WORLD_SIZE unset): one process per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, rank 0's line relayed; under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the launcher's environment is honoured as before.
 Partition (`config.partition`): "matrices" -- independent matrices on different ranks (every rank its own S x 32: weak scaling;
 north_star: "partition independent weight matrices ... RCCL all-gather of the output vectors") is `value`; the bucket-column
-split of SURVEY 8e ("columns", strong scaling) and config 4's per-layer latency case are measured beside it (`multi_gpu`).
+split of SURVEY 8e ("columns", strong scaling) and config 4's per-layer latency case are measured beside it under --full (`multi_gpu`).
 """
 from __future__ import annotations
 
@@ -328,6 +330,19 @@ class LaneJob:
 
     def last_dispatch_count(self, nsteps, idx):
         return self.ctx.last_dispatch_count(idx)
+
+
+def upload(graph):
+    """hipGraphUpload of a captured graph on the current stream: the work a graph's first launch would otherwise do, done without
+    running its steps.  Through the HIP runtime this process already has loaded (torch's): a second copy must not be opened."""
+    import ctypes
+
+    import torch
+    hip = ctypes.CDLL("libamdhip64.so.7", mode=os.RTLD_NOLOAD)
+    rc = hip.hipGraphUpload(ctypes.c_void_p(graph.raw_cuda_graph_exec()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"hipGraphUpload failed: hipError {rc}")
+    torch.cuda.synchronize()
 
 
 def time_graph(g_timed, g_warm, barrier=None, reps=1):
@@ -634,7 +649,12 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=4, help="steps (launches) in flight: the context's lanes (effort_set_overlap)")
     ap.add_argument("--partition", choices=["matrices", "columns"], default="matrices",
                     help="accepted for compatibility and ignored: N > 1 times both partitions (matrices = `value`, columns beside it in multi_gpu)")
-    ap.add_argument("--no-sweep", action="store_true", help="headline + roofline + cpu_baseline only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other section: roofline (+ in-run PMC passes), by_group_size, the reference's timing loop, "
+                         "dense baselines, effort sweep, other shapes / Q4, decode, cpu_baseline + the oracle check; N > 1: the multi_gpu legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed job's last step's outputs (32 x outDim float32) to DIR/out.npy after the timed steps")
+    ap.add_argument("--no-sweep", action="store_true", help="(--full) headline + roofline + cpu_baseline only")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes (roofline.traffic then comes from the committed profile)")
     ap.add_argument("--no-decode", action="store_true", help="skip the end-to-end decode section (BASELINE.json configs[4])")
@@ -720,20 +740,13 @@ class Bench:
         g_warm = job.capture(self.head_step, args.warmup) if args.warmup > 0 else None
         self.g_timed = job.capture(self.head_step, args.steps)
         self.D = job.last_dispatch_count(args.steps, (N_MATS - 1) % self.G)
-        # the K-step job is repeated until the timed region is >= 50 ms (a 2.5 ms region reads 5 % slow: clocks, caches).  The
-        # repetitions are captured into ONE graph, timed with one launch: a graph's lanes drain at its end, so replaying a 20-step
-        # graph spends ~7 % of its time filling and draining the four launches in flight -- an artefact of chopping the job into
-        # replays, not of the job (the K-step graph replayed `reps` times is reported beside it)
-        est = time_graph(self.g_timed, g_warm, self.barrier)
-        self.reps = reps = max(1, int(0.06 / max(est, 1e-6)) + 1)
-        self.dt_replayed = time_graph(self.g_timed, g_warm, self.barrier, reps=reps) / args.steps
-        if reps > 1:
-            g_long = job.capture(self.head_step, args.steps * reps)
-            time_graph(g_long, None)                                  # (a graph's first replay uploads it)
-            self.dt = time_graph(g_long, g_warm, self.barrier) / (args.steps * reps)
-            del g_long
-        else:
-            self.dt = self.dt_replayed
+        # the timed region is exactly the K steps asked for: ONE replay of the K-step graph after the W warm-up steps.  The graph
+        # is uploaded beforehand so that the timed replay is not its first.  (Its lanes fill and drain once per replay: a K that
+        # makes the region short reads a few % slow -- 20 steps ~3 %.)
+        upload(self.g_timed)
+        self.dt = time_graph(self.g_timed, g_warm, self.barrier) / args.steps
+        # the --full sections that time jobs of their own repeat them until they span >= 50 ms (a 2.5 ms region reads 5 % slow)
+        self.reps = max(1, int(0.06 / max(self.dt * args.steps, 1e-6)) + 1)
         self.in_flight = min(S, args.steps)
         self.dt_kernel = self.dt
 
@@ -818,15 +831,13 @@ class Bench:
         self.make_exchange()
         ex = self.Exchange(self.ew_sets, OUT_DIM)
         ex.timed(False)                                      # (first pass: every graph's first replay uploads it)
-        # as on one GPU the K-step job is repeated back to back until the timed region is >= 50 ms (the same count on every rank:
-        # from the max-over-ranks estimate); the rounds and their all-gathers simply continue across the repetitions
-        self.reps = reps = max(1, int(0.06 / max(ex.timed(True) * args.steps, 1e-6)) + 1)
-        ex.timed(False, args.steps * reps)                   # (uploads the remainder round's graph)
-        self.dt_kernel = ex.timed(False, args.steps * reps)  # the steps without the exchange (kernel only)
-        self.dt = ex.timed(True, args.steps * reps)
+        # as on one GPU the timed region is exactly the K steps asked for
+        self.dt_kernel = ex.timed(False)                     # the steps without the exchange (kernel only)
+        self.dt = ex.timed(True)
+        # the --full legs repeat their jobs until they span >= 50 ms (the same count on every rank: dt is the max over ranks)
+        self.reps = max(1, int(0.06 / max(self.dt * args.steps, 1e-6)) + 1)
         self.D = self.job.ctxs[0].last_dispatch_count((N_MATS - 1) % self.G)
         self.in_flight = min(self.S, args.steps)
-        self.dt_replayed = self.dt
         self.g_timed = None
         self.head_step = self.mul_step(args.effort, wsets=self.ew_sets)
         del ex
@@ -1181,6 +1192,15 @@ class Bench:
         return cb
 
 
+def dump_outputs(b, d):
+    """--dump-outputs DIR: what the timed job's last step hands its caller -- its 32 output vectors (output set (K-1) % S; every
+    step that writes that set multiplies the same matrices by the same input) -- as DIR/out.npy, float32 [32, outDim]."""
+    import numpy as np
+    b.torch.cuda.synchronize()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "out.npy"), b.out_sets[(b.args.steps - 1) % b.S].cpu().numpy().astype(np.float32))
+
+
 def dist_env():
     return int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
 
@@ -1235,6 +1255,8 @@ def main(argv=None):
     torch.cuda.set_device(local)
     dist = None
     if world > 1 or os.environ.get("BENCH_FORCE_DIST"):      # (the env knob exercises the collective path on a 1-GPU box)
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the one-GPU job only")
         dist = init_dist("nccl", torch.device("cuda", local))
     b = Bench(args, rank, world, local, dist)
     G, S = b.G, b.S
@@ -1242,7 +1264,7 @@ def main(argv=None):
         b.headline_dist()
     else:
         b.headline()
-    dt, D, reps = b.dt, b.D, b.reps
+    dt, D = b.dt, b.D
     calls_per_step = N_MATS * world                                  # whole job
     t_call = dt / N_MATS                                             # per-rank time per bucketMul call
     value = calls_per_step * b.eff_bytes / dt / 1e9
@@ -1265,10 +1287,12 @@ def main(argv=None):
                    "partition": "matrices" if world > 1 else "none", "dispatch_rows": D},
         "bytes_per_launch": G * kb, "us_per_call": round(t_call * 1e6, 3),
         "tokens_per_s": round(1.0 / (t_call * 4 * 32), 2),
-        "steps_requested": args.steps, "timed_steps": args.steps * reps, "timed_region_ms": round(dt * args.steps * reps * 1e3, 3), "timed_replays": 1,
-        "timed_region_note": (f"the {args.steps}-step job {reps} times back to back: rounds of {16 * S} steps (one hipGraph each), a round's all-gather under the next round's compute" if dist else
-                              f"the {args.steps}-step job {reps} times back to back in ONE hipGraph, one launch; the {args.steps}-step graph replayed {reps} times instead (its lanes drain at every replay's end): {b.dt_replayed * 1e3:.5f} ms per step"),
+        "steps_requested": args.steps, "timed_steps": args.steps, "timed_region_ms": round(dt * args.steps * 1e3, 3), "timed_replays": 1,
+        "timed_region_note": (f"the {args.steps}-step job after {args.warmup} warm-up steps: rounds of {16 * S} steps (one hipGraph each), a round's all-gather under the next round's compute" if dist else
+                              f"the {args.steps}-step job after {args.warmup} warm-up steps: ONE hipGraph (uploaded beforehand), one launch"),
     }
+    if args.dump_outputs:
+        dump_outputs(b, args.dump_outputs)
     if os.environ.get("BENCH_LAUNCHED"):
         result["launched_by"] = "bench.py --gpus N (its own launcher: launch_ranks)"
     aux_done = threading.Event()
@@ -1299,10 +1323,10 @@ def main(argv=None):
                               "unit": "GB/s", "frac": round(kbl / t_launch / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
                               "bytes_per_launch": kbl, "calls_per_launch": G, "launches_in_flight": b.in_flight, "kernel_us": round(t_launch * 1e6, 3),
                               "scope": "per rank (one GPU's HBM), slowest rank, kernel-only time of the timed rounds; the all-gather of the outputs is in ms_per_step"}
-        if not args.headline_only:
+        if args.full and not args.headline_only:
             b.multi_gpu_legs(result)
 
-    if rank == 0 and world == 1 and not args.headline_only:
+    if rank == 0 and world == 1 and args.full and not args.headline_only:
         result["roofline"] = b.roofline()
         if not args.no_sweep:
             result["by_group_size"] = by = b.by_group_size()
@@ -1481,11 +1505,12 @@ def guarded():
     """N = 1: the measurement runs in a CHILD process and this one relays its line: should the child ever die without a record, the
     contract-complete subset (headline + roofline + cpu_baseline: --no-sweep --no-pmc) is run instead, then the headline alone;
     what was dropped is named in the line's `note`.  (Round 5 added this after one run in ~40 ended in glibc's `free(): invalid
-    pointer`; DESIGN 5 has what round 6's hunt found.)"""
+    pointer`; DESIGN 5 has what round 6's hunt found.)  Only under --full: a plain run is the headline alone, and trying it again
+    would run the same job that just died."""
     import subprocess
     env = dict(os.environ, BENCH_CHILD="1")
     note = None
-    for extra in ([], ["--no-sweep", "--no-pmc"], ["--headline-only"]):
+    for extra in ([], ["--no-sweep", "--no-pmc"], ["--headline-only"]) if "--full" in sys.argv[1:] else ([],):
         p = subprocess.run([sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + extra, env=env, stdout=subprocess.PIPE)
         line = _last_record(p.stdout.decode(errors="replace"))
         if line is not None:

@@ -274,7 +274,8 @@ def test_bench_compact_line_fits_the_driver_tail():
 
 def test_bench_guard_relays_the_record_or_falls_back(monkeypatch, capsys):
     """bench.py at N = 1 measures in a child process: a child that dies without a record (an auxiliary section taking the process
-    down) is followed by the contract-complete subset, whose line is relayed with a note naming what happened."""
+    down) is followed by the contract-complete subset, whose line is relayed with a note naming what happened.  That is --full's
+    guard: a plain run is the headline alone, and one that dies is not started again."""
     import json
     import subprocess
     import sys
@@ -290,12 +291,67 @@ def test_bench_guard_relays_the_record_or_falls_back(monkeypatch, capsys):
             return types.SimpleNamespace(returncode=-6, stdout=b"RCCL banner\n")
         return types.SimpleNamespace(returncode=0, stdout=("noise\n" + json.dumps(record) + "\n").encode())
     monkeypatch.setattr(subprocess, "run", fake_run)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
     assert bench.guarded() == 0
     out = capsys.readouterr().out.strip().split("\n")
     assert len(out) == 1
     line = json.loads(out[0])
     assert line["value"] == 1.0 and "exit code -6" in line["note"]
     assert "--no-sweep" in calls[1] and "--no-sweep" not in calls[0]
+    calls.clear()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5"])
+    assert bench.guarded() == 1 and len(calls) == 1
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_plain_run_is_the_headline_alone(monkeypatch, capsys, tmp_path, full):
+    """A plain `bench.py --steps K --warmup W` sets up, times the headline and prints its line -- no other section runs; `--full`
+    runs every section after the headline.  `--dump-outputs DIR` writes the last step's output set (slot (K-1) % S) as float32.
+    bench.Bench is replaced by a recorder: the section selection of main() without a GPU."""
+    import json
+    import sys
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    calls = []
+
+    class Recorder:
+        def __init__(self, args, rank=0, world=1, local=0, dist=None):
+            self.args, self.G, self.S, self.n_sets, self.in_flight, self.launches_per_step = args, 32, 4, 4, 4, 1
+            self.eff_bytes = 2 * bench.IN_DIM * bench.OUT_DIM
+            self.torch = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+            self.ea, self.dev = types.SimpleNamespace(Gpu=lambda d: None), None
+            self.out_sets = [torch.full((bench.N_MATS, bench.OUT_DIM), float(k)) for k in range(self.S)]
+
+        def headline(self):
+            calls.append("headline")
+            self.dt, self.D, self.reps = 1e-4, 16000, 3
+
+        def __getattr__(self, name):
+            def section(*a):
+                calls.append(name)
+                return {"1": {"us_per_call": 17.0}} if name == "by_group_size" else {}
+            return section
+    for k in ("BENCH_CHILD", "BENCH_LAUNCHED", "BENCH_STUB", "BENCH_FORCE_DIST", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench, "Bench", Recorder)
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    monkeypatch.setattr(bench, "timeit_protocol", lambda *a: calls.append("timeit_protocol") or {})
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    argv = ["--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")] + (["--full"] if full else [])
+    assert bench.main(argv) == 0
+    line = json.loads(capsys.readouterr().out.strip().split("\n")[-1])
+    assert line["steps"] == line["timed_steps"] == 6 and line["warmup"] == 2 and abs(line["ms_per_step"] - 0.1) < 1e-9
+    got = np.load(tmp_path / "out" / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.N_MATS, bench.OUT_DIM) and (got == 1.0).all()    # step 5 -> slot 1
+    if full:
+        assert calls[0] == "headline" and {"roofline", "by_group_size", "timeit_protocol", "dense_baseline", "effort_sweep", "other_configs",
+                                           "decode", "cpu_check"} <= set(calls)
+    else:
+        assert calls == ["headline"]
 
 
 def _run_bench(args, env_extra, timeout=180):

@@ -349,3 +349,32 @@ def test_timed_configuration_as_a_whole(ea, oracle_cpu):
                 ctx.hook_lane(i % lanes)
                 assert ctx.last_dispatch_count(k) == n and ctx.last_cutoff(k) == cutoff, (i, k)
     ctx.close()
+
+
+def test_bench_plain_run_dumps_its_last_step(ea, oracle_cpu, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as a caller runs it: the line holds exactly K timed steps and
+    none of the --full sections, and DIR/out.npy is what the last step computed -- the 32 outputs of output set (K-1) % 4 --
+    against the oracle on the same matrices and input, rebuilt here from the bench's seeds."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    steps, lanes = 6, 4
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_CHILD", "BENCH_NO_GUARD", "BENCH_FORCE_DIST", "BENCH_STUB")}
+    p = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().split("\n")[-1])
+    assert line["steps"] == line["timed_steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "roofline" not in line and "cpu_baseline" not in line
+    got = np.load(tmp_path / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.N_MATS, bench.OUT_DIM)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(42)
+    v = torch.randn(bench.IN_DIM, generator=gen, device=DEV, dtype=torch.float32).cpu().numpy()
+    ws = bench.make_weights(ea, bench.N_MATS, bench.IN_DIM, bench.OUT_DIM, 1234 + ((steps - 1) % lanes) * bench.N_MATS, torch.device(DEV), keep_core=False)
+    for k, ew in enumerate(ws):
+        want, _, _ = oracle_cpu.bucket_mul(v, *_host(ew), bench.IN_DIM, bench.OUT_DIM, 0.25)
+        assert close(got[k], want), k

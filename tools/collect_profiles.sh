@@ -37,13 +37,13 @@ python tools/pmc_cache.py --dir $O/prof_tcc25s --out $O/${R}_pmc_tcc_effort25_sh
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/prof_fetchs -- $H --headline-shared > /dev/null 2> $O/pmc_fetchs.log
 python tools/pmc_traffic.py --fetch $O/prof_fetchs --group 32 --effort 0.25 --out $O/${R}_pmc_traffic_shared_matrices.json
 rm -rf $O/prof_bench $O/prof_bench1 $O/prof_shared $O/prof_fetch $O/prof_write $O/prof_tcc25 $O/prof_tcc10 $O/prof_tcc25s $O/prof_fetchs
-# 5. the bench line as the driver runs it, and at the default length
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_driver_style.json 2> $O/bench_driver_style.log
+# 5. the bench line with every section (--full)
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_driver_style.json 2> $O/bench_driver_style.log
 tail -c 400 $O/${R}_bench_driver_style.json
 cp $O/bench_full.json $O/${R}_bench_full.json
 # 5b. what the driver's command no longer runs (tools/bench_extra.py), and the N > 1 leg as a world of one through RCCL
 python tools/bench_extra.py --steps 20 --warmup 5 > /dev/null 2> $O/bench_extra.log; cp $O/bench_extra.json $O/${R}_bench_extra.json
-BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 > $O/${R}_bench_forced_dist_world1.json 2> $O/bench_forced_dist.log
+BENCH_FORCE_DIST=1 python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_forced_dist_world1.json 2> $O/bench_forced_dist.log
 # 6. decode loop: tokens/s and per-kernel summary
 python tools/decode_bench.py --tokens 64 > $O/${R}_decode_bench.json 2> $O/decode.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_dec -- python tools/decode_bench.py --tokens 64 --efforts 0.25 > $O/prof_dec.log 2>&1

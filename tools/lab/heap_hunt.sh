@@ -15,7 +15,7 @@ for i in $(seq 1 $RUNS); do
   t0=$(date +%s)
   if [ $MODE = bench ] || [ $MODE = both ]; then
     MALLOC_CHECK_=3 MALLOC_PERTURB_=165 LD_PRELOAD=$PRE BENCH_CHILD=1 PYTHONFAULTHANDLER=1 timeout 600 \
-      python -X faulthandler bench.py --steps 20 --warmup 5 "$@" > $OUT/bench_$i.out 2> $OUT/bench_$i.err
+      python -X faulthandler bench.py --full --steps 20 --warmup 5 "$@" > $OUT/bench_$i.out 2> $OUT/bench_$i.err
     rc=$?
     echo "run $i bench rc=$rc $(( $(date +%s) - t0 )) s" | tee -a $OUT/summary.txt
     if [ $rc -ne 0 ]; then fails=$((fails+1)); cp $OUT/bench_$i.err $OUT/FAILED_bench_$i.err; [ "${HUNT_KEEP_GOING:-0}" = 1 ] || break; else rm -f $OUT/bench_$i.err $OUT/bench_$i.out; fi

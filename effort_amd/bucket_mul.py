@@ -63,8 +63,6 @@ def _marshal(calls, q4: bool):
     extras = [c[5] if len(c) > 5 and c[5] else {} for c in calls]
     if not any(extras):
         return n, ws, vs, es, outs, eff, None, None, None
-    if q4:
-        raise ValueError("fused prologues / epilogues are implemented for FP16 bundles")
     pre, aux, res = [], [], []
     for c, x in zip(calls, extras):
         if set(x) - {"gate", "norm", "resid"} or ("gate" in x and "norm" in x):
@@ -88,7 +86,8 @@ def bucketMulGroup(calls, gpu=None):
     Q4 bundles.  Same results as calling bucketMul / bucketMulQ4 on each; the group is how independent projections of
     the decode loop (Wq|Wk|Wv, W1|W3 -- runNetwork.swift:132-134,178-182) keep the whole chip busy.
 
-    A call may carry a 6th element, a dict folding the loop's neighbouring element-wise steps into the launch (FP16):
+    A call may carry a 6th element, a dict folding the loop's neighbouring element-wise steps into the launch (FP16 and Q4;
+    a Q4 bundle with outliers takes a prologue up to 16384 inputs, see effort_bucketmul_q4_group_fused):
     ``{"gate": x3}`` -- input = silu(v) * x3 (runNetwork.swift:181); ``{"norm": w}`` -- input = rmsNorm(v) * w (:121-122);
     ``{"resid": h}`` -- out = h + product (:172,183; ``h`` may be ``out`` itself)."""
     calls = [tuple(c) for c in calls]
@@ -103,7 +102,8 @@ def bucketMulGroup(calls, gpu=None):
     g = bm.gpu
     g._bind_stream()
     if pre is not None:
-        g.check(_lib.lib().effort_bucketmul_group_fused(g.ctx, n, ws, vs, es, outs, eff, pre, aux, res), "bucketMulGroup")
+        fn = _lib.lib().effort_bucketmul_q4_group_fused if q4 else _lib.lib().effort_bucketmul_group_fused
+        g.check(fn(g.ctx, n, ws, vs, es, outs, eff, pre, aux, res), "bucketMulGroup")
         return
     fn = _lib.lib().effort_bucketmul_q4_group if q4 else _lib.lib().effort_bucketmul_group
     g.check(fn(g.ctx, n, ws, vs, es, outs, eff), "bucketMulGroup")

@@ -180,10 +180,12 @@ def convertMistral(tensors: Mapping[str, torch.Tensor], saver: TensorSaver, numL
 # ------------------------------------------------------------------------------------------------ loading
 def loadExpertWeights(loader: TensorLoader, prefix: str, wId: str | None = None, *, inDim: int | None = None,
                       outDim: int | None = None, numExperts: int = 1, percentLoad: int | None = None, q4: bool = False,
-                      device: str | torch.device = "cuda"):
+                      device: str | torch.device = "cuda", dense_ok: bool = False):
     """``ExpertWeights(elName:)`` when ``wId`` is None (names ``prefix.{core,probes,buckets,bucket.stats,outliers}``,
     shapes from the core, loader.swift:60-111) else ``ExpertWeights(prefix, wId, inDim:outDim:numExperts:percentLoad:)``
-    (names ``prefix{e}.{wId}.*``, experts stacked, only ``inDim*percentLoad`` rows per expert read, :113-166)."""
+    (names ``prefix{e}.{wId}.*``, experts stacked, only ``inDim*percentLoad`` rows per expert read, :113-166).
+    ``dense_ok``: a bundle stored as a core alone (wk, wv and wo of a Q4 model) comes back as ``ExpertWeights.core_only``
+    -- the reference's ``bucketsLoaded = false`` (loader.swift:105-107) -- instead of raising KeyError."""
     from .weights import ExpertWeights
     full = 8 if q4 else 16
     pl = full if percentLoad is None else int(percentLoad)
@@ -195,6 +197,8 @@ def loadExpertWeights(loader: TensorLoader, prefix: str, wId: str | None = None,
         outDim, inDim = core.shape
     outliers = loader[names[0] + "outliers"].to(device) if loader.hasTensor(names[0] + "outliers") else None
     if not loader.hasTensor(names[0] + "probes"):
+        if dense_ok and core is not None and len(names) == 1:
+            return ExpertWeights.core_only(core.to(torch.float16), q4=q4)
         raise KeyError(f"buckets not loaded for {names[0]} (loader.swift:104-107): dense fallback only")
     rows = inDim * pl
     probes = torch.stack([loader[n + "probes"].to(device)[:4096] for n in names])

@@ -874,7 +874,11 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
         if (!(efforts[i] >= 0.0 && efforts[i] <= 1.0)) return fail(c, EFFORT_ERR_EFFORT, "bucketmul: effort outside [0,1]");
         const int pre = prologues ? prologues[i] : 0;
         if (pre < 0 || pre > 2 || (pre && (!vAux || !vAux[i]))) return fail(c, EFFORT_ERR_ARG, "bucketmul: bad input prologue");
-        if (pre && (fmt != kFp16 || c->splitCutoff)) return fail(c, EFFORT_ERR_KIND, "bucketmul: input prologues need FP16 weights and the fused cutoff");
+        if (pre && c->splitCutoff) return fail(c, EFFORT_ERR_KIND, "bucketmul: input prologues need the fused cutoff");
+        // Q4: the outlier phase needs the whole TRANSFORMED input and keeps it in LDS; beyond that copy's size it gathers v from memory, where a prologue's
+        // input does not exist (bucket_mul.hip, phase O).  A residual alone, or a handle without outliers, works at any size.
+        if (pre && fmt == kQ4 && ws[i]->olBlockPtr && (uint32_t)ws[i]->inDim > bucket_mul_ol_lds_floats())
+            return fail(c, EFFORT_ERR_SHAPE, "bucketmul: an input prologue on a Q4 handle with outliers needs inDim <= 16384 (materialise the input, or register without outliers)");
     }
     { double sum = 0.0; for (int i = 0; i < n; i++) sum += efforts[i]; c->thinEffort = sum < 0.08 * n; }
     const int groupE = pick_elems(c, fmt, n, ws);         // columns per lane: one choice for a group launch
@@ -1180,6 +1184,11 @@ extern "C" int effort_bucketmul_group_fused(effort_ctx* c, int n, const effort_w
                                             const uint32_t* const* expNos, float* const* outs, const double* efforts,
                                             const int* prologues, const void* const* vAux, const float* const* resids) {
     return do_group(c, kFp16, n, ws, vs, expNos, outs, efforts, prologues, vAux, resids);
+}
+extern "C" int effort_bucketmul_q4_group_fused(effort_ctx* c, int n, const effort_w* const* ws, const float* const* vs,
+                                               const uint32_t* const* expNos, float* const* outs, const double* efforts,
+                                               const int* prologues, const void* const* vAux, const float* const* resids) {
+    return do_group(c, kQ4, n, ws, vs, expNos, outs, efforts, prologues, vAux, resids);
 }
 extern "C" int effort_bucketmul_q4_group(effort_ctx* c, int n, const effort_w* const* ws, const float* const* vs,
                                          const uint32_t* const* expNos, float* const* outs, const double* efforts) {

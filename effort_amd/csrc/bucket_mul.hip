@@ -440,8 +440,15 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
                 ol_share();
                 olEarly = g.inDim <= kOlEarlyFloats && lp.offO != 0u;
                 if (olEarly) {
+                    if constexpr (FUSED) {       // (under an input prologue the copy is made of the prologue's own operands, rawn / auxc below: the same eight inputs per thread)
+                        if (a.pre == (uint16_t)kPreNone) {
+#pragma unroll
+                            for (int u = 0; u < 8; u++) olVx[u] = a.v[min((uint32_t)(u * NT + tid), g.inDim - 1u)];
+                        }
+                    } else {
 #pragma unroll
                     for (int u = 0; u < 8; u++) olVx[u] = a.v[min((uint32_t)(u * NT + tid), g.inDim - 1u)];
+                    }
                     if ((uint32_t)wave < olNB * olParts) {
                         const uint32_t bq = (uint32_t)wave / olParts;
                         olMeta0 = a.ol.meta[(size_t)(olBFirst + bq) * 64u + (uint32_t)lane];
@@ -470,6 +477,7 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     // thread's element of the slice.  (Asked for where they were used -- vAux after the norm's reduction, the slice's vAux after
     // the staged loads had landed -- they were two more dependent round trips: a fused launch cost 3-4 us more than a plain one.)
     float rawn[VPT]; uint32_t auxc[VPT]; uint32_t auxS = 0u;
+    uint32_t auxS1 = 0u;                                          // (Q4 stages TWO inputs of the slice per thread, stage_issue: vAux of the second)
     const bool preAny = FUSED && pre != (uint32_t)kPreNone;       // uniform
     const bool needCutEarly = fused && cachedCall != ci;          // (= needCut below)
 #pragma unroll
@@ -489,6 +497,21 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
         }
         const uint32_t js = j0 + min((uint32_t)tid, nb - 1u);
         auxS = gate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + js)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[js];
+        if constexpr (FUSED && FMT != kFp16) {
+            const uint32_t js1 = j0 + min((uint32_t)(tid + NT), nb - 1u);
+            auxS1 = gate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + js1)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[js1];
+            // Q4 with outliers: the early LDS copy of the whole input (olEarly: inDim = 4096) must hold the TRANSFORMED input, so the operands
+            // of the first 4096 inputs are asked for whether or not this item evaluates the cutoff
+            if (olEarly && !needCutEarly) {
+                if (gate) {
+#pragma unroll
+                    for (int i = 0; i < VPT; i++) rawn[i] = *(a.v + tid + NT * i);
+                }
+#pragma unroll
+                for (int i = 0; i < VPT; i++)
+                    auxc[i] = gate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + tid + NT * i)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[tid + NT * i];
+            }
+        }
     }
     const uint32_t lg = g.sliceLog2;
     const uint32_t nSlots = FMT == kFp16 ? (g.rowsPerIn << lg) : (nb << 3);
@@ -576,7 +599,10 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
         if (olEarly) {                                                // (published by the barrier of B, with vblk)
             float* const vf = reinterpret_cast<float*>(smem + __builtin_amdgcn_readfirstlane(lp.offO));
 #pragma unroll
-            for (int u = 0; u < 8; u++) if ((uint32_t)(u * NT + tid) < g.inDim) vf[u * NT + tid] = olVx[u];
+            for (int u = 0; u < 8; u++) {
+                if constexpr (FUSED) { if ((uint32_t)(u * NT + tid) < g.inDim) vf[u * NT + tid] = preAny ? xform(rawn[u % VPT], auxc[u % VPT]) : olVx[u]; }      // (kOlMerge: W = 8, VPT = 8 -- rawn[u] is input u * NT + tid)
+                else if ((uint32_t)(u * NT + tid) < g.inDim) vf[u * NT + tid] = olVx[u];
+            }
         }
     }
     float bound = 0.0f;
@@ -585,6 +611,8 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
         const uint32_t jl = tid + u * NT;
         if (jl < nb) {
             float x = vblk[jl];
+            if constexpr (FUSED && FMT != kFp16) { if (preAny) { x = xform(x, u ? auxS1 : auxS); vblk[jl] = x; } }      // (jl = tid + u * NT: the element auxS / auxS1 was loaded for)
+            else
             if (preAny) { x = xform(x, auxS); vblk[jl] = x; }       // (FP16: u == 0, jl == tid: the element auxS was loaded for)
             bound += fabsf(x);
         }
@@ -979,6 +1007,23 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
                     float x[8];
 #pragma unroll
                     for (int u = 0; u < 8; u++) x[u] = a.v[min(i0 + u * NT + tid, g.inDim - 1u)];
+                    if constexpr (FUSED) {                                                 // the copy holds the input the multiply saw: the prologue's partners, beside the inputs
+                        uint32_t xa[8];
+#pragma unroll
+                        for (int u = 0; u < 8; u++) xa[u] = 0u;
+                        if (preAny) {
+#pragma unroll
+                            for (int u = 0; u < 8; u++) {
+                                const uint32_t i = min(i0 + u * NT + tid, g.inDim - 1u);
+                                xa[u] = pre == (uint32_t)kPreSiluGate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + i)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[i];
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < 8; u++) {
+                            const uint32_t i = i0 + u * NT + tid;
+                            if (i < g.inDim) vfull[i] = preAny ? xform(x[u], xa[u]) : x[u];
+                        }
+                    } else
 #pragma unroll
                     for (int u = 0; u < 8; u++) {
                         const uint32_t i = i0 + u * NT + tid;
@@ -1272,8 +1317,10 @@ __device__ __forceinline__ void cutoff_job(const GroupKArgs& ga, uint32_t ci, ch
 // R fixed by the LDS each one asks for -- and balances the work itself.
 // (Round 4's CHAIN instantiation -- a layer's dependent multiplies as stages of ONE launch, measured 22 % slower than the launches of
 //  their own -- lives on branch `chain-launch`: DESIGN.md 4.5.)
+// (Q4 with prologues at W = 2 -- a debug geometry, 32 inputs of the cutoff per thread AND their prologue operands held beside the outlier
+//  stepper's state -- does not fit 128 VGPRs without a scratch segment: that one instantiation is budgeted two waves per SIMD)
 template <int FMT, int E, int W, bool FUSED, bool COMPACT = false, bool PERSIST = true>
-__global__ __launch_bounds__(64 * W, (W <= 8 ? EFFORT_MIN_WAVES_PER_EU : 4)) void bucket_mul_kernel(const GroupKArgs ga) {
+__global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <= 8 ? EFFORT_MIN_WAVES_PER_EU : 4)) void bucket_mul_kernel(const GroupKArgs ga) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ uint32_t s_item;
     __shared__ unsigned long long s_next;                  // the item after the current one | the generation (item count) it was pulled in << 32: ONE word,
@@ -1347,7 +1394,7 @@ __global__ __launch_bounds__(64 * W, (W <= 8 ? EFFORT_MIN_WAVES_PER_EU : 4)) voi
     // pulls item i+1 from the queue and publishes it in LDS (s_next: item, generation); every wave that finds it there
     // issues its share of item i+1's stage loads (row means + slice of v, stage_issue) under its remaining rows.  A wave that
     // finishes its rows before the answer is there stages its share at the start of item i+1 instead.
-    constexpr bool kPipe = !FUSED && FMT == kFp16;         // (a fused input prologue transforms v in place; Q4's outlier phase reuses the staging region)
+    constexpr bool kPipe = !FUSED && FMT == kFp16;         // (a fused input prologue transforms v in place; Q4's outlier phase reuses the staging region -- under a prologue for its transformed copy of v)
     const LdsPlan lp = ga.lp;                              // (the launcher's plan_lds<FMT, E, W> over ga.geom)
     uint32_t par = 0;                                      // vblk buffer of the current item
     bool staged = false;                                   // (per wave) its share of the item's stage loads is already in flight / landed
@@ -1433,7 +1480,9 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
     }
     bool fusedAny = false;
     for (uint32_t i = 0; i < ga.count; i++) fusedAny = fusedAny || ga.call[i].pre || ga.call[i].resid;
-    if (fusedAny && FMT != kFp16) return hipErrorInvalidValue;
+    // (Q4: a prologue on a call whose outliers gather v from memory -- inDim > kOlLdsFloats -- would add the outliers of the RAW input: api.hip refuses it)
+    for (uint32_t i = 0; FMT != kFp16 && i < ga.count; i++)
+        if (ga.call[i].pre && ga.call[i].ol.blockPtr && ga.geom[ga.call[i].geom].inDim > kOlLdsFloats) return hipErrorInvalidValue;
     // (every instantiation may use the whole LDS: bucket_mul_prepare_device, once per device at effort_create)
     if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
     const bool compact = (ga.split & 4u) != 0u;                   // (api.hip: persistent FP16 launches of plain calls)
@@ -1442,10 +1491,10 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
     if constexpr (kLean) {
         if (lean && compact && fusedAny) { hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, true, true, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
         if (lean && compact) { hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, false, true, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
-        if (lean && fusedAny) { hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, true, false, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
+        if (lean && fusedAny) { hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, true, false, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
         if (lean) { hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, false, false, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
     }
-    if (fusedAny) hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, true>), gd, bd, lds, st, ga);
+    if (fusedAny) hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, true>), gd, bd, lds, st, ga);
     else if (compact) hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, false, true>), gd, bd, lds, st, ga);
     else hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, false>), gd, bd, lds, st, ga);
     return hipGetLastError();
@@ -1468,6 +1517,10 @@ static hipError_t prepare_t() {
     constexpr bool kLean = W == 8;
     hipError_t err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, false>));
     if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, false, false, false>));
+    if constexpr (FMT != kFp16) {              // Q4 with prologues / residual: generic and lean plain (COMPACT is FP16 only)
+        if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, true>));
+        if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, true, false, false>));
+    }
     if constexpr (FMT == kFp16) {
         if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, true>));
         if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, false, true>));
@@ -1519,6 +1572,8 @@ int bucket_mul_occupancy(Format fmt, int W, int E, size_t ldsBytes) {
 #undef EFFORT_CASE
     return n;
 }
+
+uint32_t bucket_mul_ol_lds_floats() { return kOlLdsFloats; }
 
 uint32_t bucket_mul_max_candidates(int W) { return (uint32_t)kRounds * 64u * (uint32_t)W; }
 

@@ -216,6 +216,7 @@ hipError_t bucket_mul_prepare_device();     // once per device: the kernels may 
 hipError_t launch_find_cutoff_group(const GroupKArgs& ga, hipStream_t st);    // ga.cutoff[i] of every call
 size_t bucket_mul_lds_bytes(Format fmt, int wavesPerGroup, int elemsPerLane, const MulGeom& g, bool lean);    // lean: with the lean Q4 kernels' region for v (plan_lds)
 uint32_t bucket_mul_max_candidates(int wavesPerGroup);
+uint32_t bucket_mul_ol_lds_floats();        // Q4: the largest inDim whose input the outlier phase keeps whole in LDS (beyond it: gathered from memory)
 int bucket_mul_occupancy(Format fmt, int wavesPerGroup, int elemsPerLane, size_t ldsBytes);
   // rowsPerIn*sliceRows must not exceed this
 

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .bucket_mul import basicMul, bucketMul, bucketMulGroup
+from .bucket_mul import basicMul, bucketMul, bucketMulGroup, bucketMulQ4
 from .runtime import gpu as _gpu
 from .weights import ExpertWeights
 
@@ -53,12 +53,16 @@ class Model:
 
     @classmethod
     def random(cls, cfg: MistralConfig, seed: int = 0, device="cuda", scale: float = 0.02, keep_cores: bool = True,
-               structured: bool = False) -> "Model":
+               structured: bool = False, q4: bool = False) -> "Model":
         """Random-init weights of the architecture (no checkpoints here), converted by the GPU bucketizer.
         ``structured``: the statistics trained transformers show and i.i.d. Gaussians lack -- heavy-tailed weights with
         per-input-channel and per-output scale spread, norm weights with a few outlier channels (so the normalised state
         a multiply sees is heavy-tailed), a peaked output distribution -- see ``structured_matrix``.  The reference's quality
-        figures (cos-sim 0.99 at 25 % effort, docs/ryc/ryc0.3.png) are for such weights; on Gaussian ones 25 % gives 0.94."""
+        figures (cos-sim 0.99 at 25 % effort, docs/ryc/ryc0.3.png) are for such weights; on Gaussian ones 25 % gives 0.94.
+        ``q4``: the reference's Q4 model (q4_convert.py:48-66) from the SAME matrices the FP16 model of this seed has: wq, w1, w2
+        and w3 through the GPU Q4 converter (2 % outliers, cores kept), wk, wv and wo as cores only."""
+        if q4 and (cfg.numExperts > 1 or not keep_cores):
+            raise ValueError("Model.random(q4=True): Mistral only (one expert), cores kept -- wk, wv and wo ARE their cores")
         m = cls(cfg)
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
@@ -75,7 +79,10 @@ class Model:
 
         kv = cfg.numHeadsKV * cfg.headDim
 
-        def bundle(o, i, experts=1):
+        def bundle(o, i, experts=1, name=""):
+            if q4:
+                core = mat(o, i)
+                return ExpertWeights.from_core_q4(core) if name in ("wq", "w1", "w2", "w3") else ExpertWeights.core_only(core, q4=True)
             ews = []
             for _ in range(experts):
                 ew = ExpertWeights.from_core(mat(o, i))
@@ -95,9 +102,9 @@ class Model:
             L.attnNorm, L.ffnNorm = vec(cfg.stateDim), vec(cfg.stateDim)
             for name, (o, i) in (("wq", (cfg.stateDim, cfg.stateDim)), ("wk", (kv, cfg.stateDim)), ("wv", (kv, cfg.stateDim)),
                                  ("wo", (cfg.stateDim, cfg.stateDim))):
-                setattr(L, name, bundle(o, i))
+                setattr(L, name, bundle(o, i, name=name))
             for name, (o, i) in (("w1", (cfg.hiddenDim, cfg.stateDim)), ("w3", (cfg.hiddenDim, cfg.stateDim)), ("w2", (cfg.stateDim, cfg.hiddenDim))):
-                setattr(L, name, bundle(o, i, cfg.numExperts))
+                setattr(L, name, bundle(o, i, cfg.numExperts, name=name))
             L.ffnGate = mat(cfg.numExperts, cfg.stateDim) * 10 if cfg.numExperts > 1 else None     # f16 [numExperts, stateDim]
             m.layers.append(L)
         m.norm = vec(cfg.stateDim)
@@ -106,19 +113,22 @@ class Model:
         return m
 
     @classmethod
-    def load(cls, loader, cfg: MistralConfig, percentLoad: int = 16, device="cuda") -> "Model":
-        """From a bucketed model on disk (effort_amd.bucketfile, names of convert.swift:70-105)."""
+    def load(cls, loader, cfg: MistralConfig, percentLoad: int = 16, device="cuda", q4: bool = False) -> "Model":
+        """From a bucketed model on disk (effort_amd.bucketfile, names of convert.swift:70-105).  ``q4``: a model written by
+        ``convertMistral(q4=True)`` (q4_convert.py:48-66): Q4 bundles, and core-only bundles where no buckets were stored."""
         from .bucketfile import loadExpertWeights
+        if q4 and cfg.numExperts > 1:
+            raise ValueError("Model.load(q4=True): the Q4 converter is Mistral only (one expert)")
         m = cls(cfg)
         for n in range(cfg.numLayers):
             L = Layer()
             L.attnNorm = loader[f"layers.{n}.attention_norm"].to(device=device, dtype=torch.float16)
             L.ffnNorm = loader[f"layers.{n}.ffn_norm"].to(device=device, dtype=torch.float16)
             for s in "qkvo":
-                setattr(L, "w" + s, loadExpertWeights(loader, f"layers.{n}.attention.w{s}", device=device))
+                setattr(L, "w" + s, loadExpertWeights(loader, f"layers.{n}.attention.w{s}", device=device, q4=q4, dense_ok=q4))
             for w, (o, i) in (("w1", (cfg.hiddenDim, cfg.stateDim)), ("w3", (cfg.hiddenDim, cfg.stateDim)), ("w2", (cfg.stateDim, cfg.hiddenDim))):
                 setattr(L, w, loadExpertWeights(loader, f"layers.{n}.feed_forward.experts.", w, inDim=i, outDim=o, numExperts=cfg.numExperts,
-                                                percentLoad=percentLoad, device=device))
+                                                percentLoad=None if q4 else percentLoad, device=device, q4=q4))
             gate = f"layers.{n}.feed_forward.gate"
             L.ffnGate = loader[gate].to(device=device, dtype=torch.float16) if cfg.numExperts > 1 and loader.hasTensor(gate) else None
             m.layers.append(L)
@@ -152,12 +162,30 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# What ``Decoder(fused_glue=None)`` folds into the launches of a model with Q4 bundles (see Decoder.__init__): nothing -- folding gate +
+# residual into the Q4 w2 launch measured 281 against 299 tokens/s.
+Q4_FUSED_DEFAULT = ()
+
+
 class Decoder:
     """State of one sequence (the globals of main.swift:78-140: h, xq, KV caches, scores ...) + the token step."""
 
-    def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=True,
+    def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
                  world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False):
         cfg = self.cfg = model.cfg
+        # A model with Q4 or core-only bundles (Model.random(q4=True) / Model.load(q4=True)): token_step dispatches per BUNDLE
+        # (_token_step_bundles); an all-FP16 model takes exactly the paths below.
+        self.mixed = any(ew.q4 or not ew.bucketsLoaded for L in model.layers for ew in (L.wq, L.wk, L.wv, L.wo, L.w1, L.w2, L.w3))
+        if self.mixed and (cfg.numExperts > 1 or any(L.ffnGate is not None for L in model.layers)):
+            raise ValueError("Decoder: Q4 decode is Mistral only (numExperts == 1; the reference's Q4 converter writes no Mixtral model)")
+        if self.mixed and (sharded or emulate_world or int(world) > 1):
+            raise ValueError("Decoder: column-sharded decode (sharded / emulate_world) is implemented for FP16 models")
+        # fused_glue=None: the default -- everything folded for FP16 models (below); for Q4 models what Q4_FUSED_DEFAULT names: NOTHING.
+        # Measured at Mistral-7B shapes, 25 % effort, 64 tokens (tools/bench_extra.py --sections decode_q4): 299 tokens/s with the glue
+        # kernels against 281 with gate + residual folded into the Q4 w2 launch (effort_bucketmul_q4_group_fused).  Opt in with
+        # fused_glue=True or a tuple of parts; the logits are the same within 2e-3 either way (bit-identical on the test model).
+        if fused_glue is None:
+            fused_glue = Q4_FUSED_DEFAULT if self.mixed else True
         # (Round 4's `chain=True` -- a layer's dependent multiplies as ONE launch of resident workgroups -- measured 252 against 308
         #  tokens/s and lives on branch `chain-launch`: DESIGN.md 4.5.)
         self.fused_attention = bool(fused_attention)      # rope + cache + attention in one launch per layer (else two)
@@ -229,6 +257,8 @@ class Decoder:
 
         ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
         delta = None
+        if self.mixed and not dense:
+            return self._token_step_bundles(effort)
         if self.sharded and not dense:
             G = self.groups
             for n, L in enumerate(m.layers):
@@ -323,6 +353,70 @@ class Decoder:
                     bucketMulGroup([(self.x2, L.w2, e0, self.ffnOut, effort), (self.x2b, L.w2, e1, self.ffnOutB, effort)])
                 ck(lib.effort_mix2(g.ctx, _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), _p(self.ffnMix), cfg.stateDim), "mix2")
                 delta = self.ffnMix
+        ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
+        basicMul(self.outNormed, m.output, self.logits)                                               # :222
+        ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+
+    def _token_step_bundles(self, effort: float):
+        """The token step of a model whose bundles are not all FP16, dispatched per bundle as expertMul does (expertMul.swift:24-38):
+        a Q4 bundle with buckets -> the Q4 multiply, a core-only bundle -> dense basicMul, an FP16 bundle -> bucketMul.  Bundles of
+        one kind that share an input share ONE group launch (w1|w3).  Glue folds into a launch where the BUNDLES allow it: the norm
+        prologue needs every consumer of the normalised input bucketed (a dense neighbour reads it from memory) and no pending
+        residual delta; the residual epilogue and the gate need a bucketed wo / w2.  The reference's Q4 layout (wk, wv, wo dense)
+        therefore folds gate + resid into w2 only; a model whose wo is bucketed too folds the norms as well."""
+        cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
+        ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
+        fn, fg, fr = "norm" in self.fuse, "gate" in self.fuse, "resid" in self.fuse
+        bucketed = lambda *ews: all(ew.bucketsLoaded for ew in ews)                 # noqa: E731
+
+        def muls(v, items):                                # items: [(ew, out, extras)]
+            for q4 in (True, False):
+                calls = [(v, ew, None, out, effort, x) for ew, out, x in items if ew.bucketsLoaded and ew.q4 == q4]
+                if len(calls) == 1 and not calls[0][5]:
+                    (bucketMulQ4 if q4 else bucketMul)(v, calls[0][1], None, calls[0][3], effort)
+                elif calls:
+                    bucketMulGroup(calls)
+            for ew, out, x in items:
+                if not ew.bucketsLoaded:
+                    assert not x, "glue folds into bucketed multiplies only"
+                    basicMul(v, ew.core, out)
+
+        ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
+        delta = None
+        for n, L in enumerate(m.layers):
+            qkv = ((L.wq, self.xq_temp), (L.wk, self.xk_temp), (L.wv, self.xv_temp))
+            if fn and delta is None and bucketed(L.wq, L.wk, L.wv):                                   # :121-134
+                muls(self.h, [(ew, out, {"norm": L.attnNorm}) for ew, out in qkv])
+            else:
+                ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(L.attnNorm), _p(self.h_norm), cfg.stateDim), "rmsnorm")
+                delta = None
+                muls(self.h_norm, [(ew, out, None) for ew, out in qkv])
+            ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
+                                         _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
+                                         C.c_float(cfg.ropeBase)), "rope_attention")
+            if fr and bucketed(L.wo):
+                muls(self.attnOutput, [(L.wo, self.h, {"resid": self.h})])                           # :170-172, h += wo(attn)
+                d2 = None
+            else:
+                muls(self.attnOutput, [(L.wo, self.attnFfnOut, None)])
+                d2 = self.attnFfnOut
+            if fn and d2 is None and bucketed(L.w1, L.w3):                                            # :173-179
+                muls(self.h, [(L.w1, self.x1, {"norm": L.ffnNorm}), (L.w3, self.x3, {"norm": L.ffnNorm})])
+            else:
+                ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(d2), _p(L.ffnNorm), _p(self.fxn), cfg.stateDim), "rmsnorm")
+                muls(self.fxn, [(L.w1, self.x1, None), (L.w3, self.x3, None)])
+            extra = {}
+            if fg and bucketed(L.w2):
+                src, extra = self.x1, {"gate": self.x3}
+            else:
+                ck(lib.effort_silu_mul(g.ctx, _p(self.x1), _p(self.x3), _p(self.x2), cfg.hiddenDim), "silu")
+                src = self.x2
+            if fr and bucketed(L.w2):
+                muls(src, [(L.w2, self.h, dict(extra, resid=self.h))])                               # :181-183, h += w2(silu), in place
+                delta = None
+            else:
+                muls(src, [(L.w2, self.ffnOut, extra or None)])
+                delta = self.ffnOut
         ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
         basicMul(self.outNormed, m.output, self.logits)                                               # :222
         ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")

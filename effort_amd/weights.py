@@ -67,6 +67,8 @@ class ExpertWeights:
     @property
     def handle(self):
         """effort_w* registered with the context (lazily, once)."""
+        if not self.bucketsLoaded:
+            raise ValueError("a core-only bundle has no buckets to register: it multiplies through basicMul (expertMul.swift:29-31)")
         if self._handle is None:
             g, lib = self._gpu, _lib.lib()
             g._bind_stream()
@@ -103,6 +105,37 @@ class ExpertWeights:
         bucketize(core, "", tensors, goQ8=False, rowPitch=aligned_row_pitch(core.shape[0]) if aligned else 0)
         return cls(tensors["buckets"], tensors["bucket.stats"], tensors["probes"], inSize=core.shape[1],
                    outSize=core.shape[0], core=core)
+
+    @classmethod
+    def core_only(cls, core: torch.Tensor, q4: bool = True) -> "ExpertWeights":
+        """A bundle whose buckets were not loaded (loader.swift:105-107): the dense f16 ``core`` [outSize, inSize] alone,
+        ``bucketsLoaded = False``, no handle.  ``expertMul`` sends it to ``basicMul`` (expertMul.swift:29-31); it is what wk, wv
+        and wo of a Q4 model are (q4_convert.py:53)."""
+        if not (core.dim() == 2 and core.element_size() == 2):
+            raise ValueError("core must be a 16-bit matrix [outSize, inSize]")
+        ew = object.__new__(cls)
+        ew.q4 = bool(q4)
+        ew.outSize, ew.inSize = int(core.shape[0]), int(core.shape[1])
+        ew.percentLoad = 8 if q4 else 16
+        ew.numExperts = 1
+        ew.core = core.contiguous()
+        ew.outliers = None
+        ew.bucketsLoaded = False
+        ew.buckets = ew.stats = ew.probes = None
+        ew.rowPitch = 0
+        ew._gpu = _gpu(core.device.index) if core.is_cuda else None      # (a host tensor: a bundle read back for inspection, never multiplied)
+        ew._handle = None
+        return ew
+
+    @classmethod
+    def from_core_q4(cls, core: torch.Tensor, perc: float = 0.02) -> "ExpertWeights":
+        """Dense f16 matrix [outSize, inSize] -> Q4 bundle via the GPU Q4 converter (q4_convert.py:54,63: convert(W.T)), the
+        top ``perc`` of the weights kept as outliers, the core kept."""
+        from .q4 import convert
+        t = convert(core.t().contiguous(), perc)
+        outl = t["outliers"] if t["outliers"].shape[0] else None
+        return cls(t["buckets"], t["bucket.stats"], t["probes"], inSize=core.shape[1], outSize=core.shape[0], outliers=outl,
+                   core=core, q4=True)
 
     @classmethod
     def stack(cls, experts: list["ExpertWeights"]) -> "ExpertWeights":

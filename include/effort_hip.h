@@ -71,7 +71,7 @@ EFFORT_API int effort_sync(effort_ctx* ctx);
  *     ranges of v / expNo / aux / resid / out are compared);
  * otherwise it runs beside the multiplies still in flight: the head of one launch (staging, cutoffs, selection: HBM idle)
  * hides under the streaming of the others (one 32-call launch after another, each on its own matrices: 0.60 -> 0.70 of the
- * HBM roofline).  Results are bit-identical.  The multiplies become visible to the context's stream at effort_join (enqueues waits, returns at
+ * HBM roofline).  Results are bit-identical for FP16 and outlier-free Q4 bundles (Q4 outlier sums: see effort_bucketmul_q4).  The multiplies become visible to the context's stream at effort_join (enqueues waits, returns at
  * once), and implicitly at effort_sync, at any other effort_* call on the context and at the test hooks.  A caller who
  * enqueues its OWN work on the stream to consume an output calls effort_join first; inside a hipGraph capture call
  * effort_join before ending the capture (the lanes fork from and must rejoin the capturing stream).
@@ -176,7 +176,9 @@ EFFORT_API int effort_bucketmul(effort_ctx* ctx, const effort_w* w, const float*
  * splits them among the waves of its workgroup, the partial sums added in wave order.  How they are split follows the launch geometry
  * (group size, the device's CU count, a column shard against the full handle), so a bundle WITH outliers gives bit-identical results
  * run to run for one geometry, and results that may differ in the last bits between a lone call, a grouped call and a column shard
- * (all within the 2e-5 * max|out| bar).  Without outliers Q4 is as order-free as FP16. */
+ * (all within the 2e-5 * max|out| bar).  The split also follows the effort_set_overlap setting (a context with lanes picks other
+ * launch geometries) and, in a group, the efforts of the group's calls (a thin group is sliced differently): the same call in another
+ * group, or under another lanes setting, may differ in those last bits too.  Without outliers Q4 is as order-free as FP16. */
 EFFORT_API int effort_bucketmul_q4(effort_ctx* ctx, const effort_w* w, const float* v_dev, const uint32_t* expNo_dev,
                         float* out_dev, double effort);
 
@@ -218,6 +220,18 @@ EFFORT_API int effort_bucketmul_group_fused(effort_ctx* ctx, int n, const effort
                                  const int* prologues, const void* const* v_aux_dev, const float* const* resids_dev);
 EFFORT_API int effort_bucketmul_q4_group(effort_ctx* ctx, int n, const effort_w* const* ws, const float* const* vs_dev,
                               const uint32_t* const* expNos_dev, float* const* outs_dev, const double* efforts);
+/* effort_bucketmul_q4_group with the same prologues and residual epilogue as effort_bucketmul_group_fused, for Q4 bundles: the
+ * argument contract is that entry's (prologues / v_aux_dev / resids_dev may be NULL or hold 0 / NULL entries; resid may alias
+ * outs[i]; refused with EFFORT_ERR_KIND after effort_set_split_cutoff; effort_bucketmul_group_fused itself keeps refusing Q4
+ * handles with EFFORT_ERR_KIND).  The derived input is what effort_silu_mul / effort_add_rmsnorm_mul would have written, bit for
+ * bit, so cutoff and row selection equal the materialise-first path's exactly; out = resid + (fixed-point sum + outlier sum), one
+ * f32 add of the finished product, and nothing is stored to out before resid has been read.
+ * OUTLIERS: calcOutliers needs the whole derived input, which the kernel keeps in LDS for inDim <= 16384.  A handle WITH outliers
+ * and inDim > 16384 that carries a prologue is refused with EFFORT_ERR_SHAPE (nothing is enqueued): materialise the input with
+ * the glue kernel, or register the bundle without outliers.  Without outliers, or with a residual alone, any size works. */
+EFFORT_API int effort_bucketmul_q4_group_fused(effort_ctx* ctx, int n, const effort_w* const* ws, const float* const* vs_dev,
+                                    const uint32_t* const* expNos_dev, float* const* outs_dev, const double* efforts,
+                                    const int* prologues, const void* const* v_aux_dev, const float* const* resids_dev);
 EFFORT_API int effort_group_dispatch_count(effort_ctx* ctx, int idx, uint32_t* host_out);
 EFFORT_API int effort_group_cutoff(effort_ctx* ctx, int idx, float* host_out);
 

@@ -2,7 +2,8 @@
 """tools/bench_extra.py -- the sections round 5's bench.py carried behind the headline and the driver's one command no longer runs
 (VERDICT r05 item 7): `by_streams`, `shared_matrices`, `four_contexts`, the timeit-protocol variants, the quality sweeps
 (heavy-tailed input, a structured matrix, the structured decode model), the other shapes, `shard_projection` (BASELINE config 4's
-column split projected on one GPU) and the one-GPU `layer_latency` (a world of one through RCCL + projected ranks).
+column split projected on one GPU), the one-GPU `layer_latency` (a world of one through RCCL + projected ranks) and `decode_q4` (the
+decode loop on the reference's Q4 model beside the FP16 one).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -19,7 +20,7 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency")
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4")
 
 
 def by_streams(b, res):
@@ -215,6 +216,52 @@ def decode_quality(b, res):
     del dec, model
 
 
+def decode_q4(b, res):
+    """The decode loop on the reference's Q4 model (q4_convert.py:48-66: wq, w1, w2, w3 in Q4 with 2 % outliers; wk, wv, wo dense)
+    beside the FP16 model of the same matrices: tokens/s at Mistral-7B shapes over 64 tokens -- dense, FP16 at 25 %, Q4 at 25 % with
+    the glue folded into the Q4 launches (gate + residual into w2) and without -- and the bytes of both models' bucket data."""
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    b.g.set_tuning(0, 0, 0)
+    torch.cuda.empty_cache()
+    prompt, nt = [1, 733, 16289, 28793, 22557], 64
+    names = ("wq", "wk", "wv", "wo", "w1", "w2", "w3")
+
+    def nbytes(model):
+        bk = sum(getattr(L, n).buckets.numel() * 2 for L in model.layers for n in names if getattr(L, n).bucketsLoaded)
+        aux = sum(getattr(L, n).stats.numel() * getattr(L, n).stats.element_size() + (0 if getattr(L, n).outliers is None else getattr(L, n).outliers.shape[0] * 4)
+                  for L in model.layers for n in names if getattr(L, n).bucketsLoaded)       # (outliers: four bytes each once registered)
+        cores = sum(getattr(L, n).core.numel() * 2 for L in model.layers for n in names if not getattr(L, n).bucketsLoaded)
+        return {"buckets": bk, "stats_and_outlier_index": aux, "dense_cores_of_core_only_bundles": cores}
+
+    def tps(dec, **kw):
+        best = 0.0
+        for _ in range(3):
+            _, dt, _ = dec.run(prompt, nt, **kw)
+            best = max(best, 1 / dt)
+        return round(best, 1)
+    out = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "tokens": nt, "protocol": "best of 3 runs of 64 tokens, hipGraph replay, timed from the 3rd step"}
+    model = Model.random(MistralConfig(), seed=1)
+    dec = Decoder(model, maxTokens=nt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+    out["dense_tokens_per_s"] = tps(dec, dense=True)
+    out["fp16_effort_0.25_tokens_per_s"] = tps(dec, effort=0.25)
+    out["fp16_bytes"] = nbytes(model)
+    del dec, model
+    torch.cuda.empty_cache()
+    model = Model.random(MistralConfig(), seed=1, q4=True)
+    out["q4_bytes"] = nbytes(model)
+    for key, fg in (("q4_effort_0.25_unfused_tokens_per_s", False), ("q4_effort_0.25_fused_gate_resid_tokens_per_s", True)):
+        dec = Decoder(model, maxTokens=nt + 8, fused_glue=fg)
+        B._GRAPHS_FOR_LIFE.append(dec._graphs)
+        out[key] = tps(dec, effort=0.25)
+        if not fg:
+            out["q4_model_dense_tokens_per_s"] = tps(dec, dense=True)
+        del dec
+    res["decode_q4"] = out
+    del model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -229,7 +276,7 @@ def layer_latency(b, res):
 
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
-       "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency}
+       "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4}
 
 
 def main():

@@ -2,7 +2,7 @@
 """A/B of decode-loop speed under library knobs, one model build: tokens/s dense (own GEMV) and effort runs with the
 row prefetch of lone calls on / off.
 
-    python tools/lab/decode_ab.py [--layers 32] [--tokens 48] [--efforts 0.25,1.0]
+    python tools/lab/decode_ab.py [--layers 32] [--tokens 48] [--efforts 0.25,1.0] [--q4] [--fused-glue gate,resid]
 """
 import argparse
 import json
@@ -23,9 +23,10 @@ def main():
     ap.add_argument("--fused-glue", default="", help="comma list of norm,gate,resid (or 1 = all) folded into the multiplies")
     ap.add_argument("--tunes", default="0,0,0", help="semicolon list of set_tuning triples (waves,elems,slices) to time, e.g. 0,0,0;8,1,0")
     ap.add_argument("--split", type=int, default=0, help="also time every knob set with the cutoffs in a kernel of their own")
+    ap.add_argument("--q4", action="store_true", help="the reference's Q4 model (wq, w1, w2, w3 in Q4; wk, wv, wo dense) instead of the FP16 one")
     a = ap.parse_args()
     torch.cuda.set_device(0)
-    model = Model.random(MistralConfig(numLayers=a.layers), seed=1)
+    model = Model.random(MistralConfig(numLayers=a.layers), seed=1, q4=a.q4)
     fg = True if a.fused_glue == "1" else tuple(x for x in a.fused_glue.split(",") if x)
     dec = Decoder(model, maxTokens=max(64, a.tokens + 8), fused_glue=fg)
     prompt = [1, 733, 16289, 28793, 22557]

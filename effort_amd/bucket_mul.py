@@ -120,6 +120,24 @@ def basicMul(v: torch.Tensor, by: torch.Tensor, out: torch.Tensor, gpu=None):
     g.check(_lib.lib().effort_dense_gemv(g.ctx, _p(by), _p(v), _p(out), by.shape[1], by.shape[0]), "basicMul")
 
 
+def basicMulExpert(v: torch.Tensor, cores: torch.Tensor, expNo: torch.Tensor, out: torch.Tensor, gpu=None):
+    """``basicMul`` on expert ``expNo`` (a DEVICE scalar, as the multiplies take it) of a stack of cores [numExperts, outDim, inDim]:
+    the dense baseline of a routed FFN, without gathering the expert's matrix first.  Bit-identical with ``basicMul(v, cores[e], out)``
+    on the package's own kernel; an expert number past the stack is clamped to the last expert.  Always that kernel: a shape it does
+    not serve raises (EFFORT_ERR_SHAPE)."""
+    assert cores.dim() == 3 and cores.shape[1] == out.numel() and cores.shape[2] == v.numel() and cores.shape[2] % 16 == 0
+    _check_vec("v", v, cores.shape[2])
+    _check_vec("out", out, cores.shape[1])
+    assert cores.is_cuda and cores.element_size() == 2 and cores.is_contiguous()
+    if expNo is None:
+        raise ValueError("basicMulExpert needs expNo (a device scalar); one matrix alone goes through basicMul")
+    _check_expno(expNo)
+    g = gpu if gpu is not None else _gpu(v.device.index)
+    g._bind_stream()
+    g.check(_lib.lib().effort_dense_gemv_expert(g.ctx, _p(cores), _p(expNo), _p(v), _p(out), cores.shape[2], cores.shape[1], cores.shape[0]),
+            "basicMulExpert")
+
+
 def expertMul(v: torch.Tensor, by: ExpertWeights, out: torch.Tensor, effort: float = 0.25, expNo: torch.Tensor | None = None):
     """expertMul.swift:24-38: Q4 bundle -> (out.zero() +) bucketMulQ4, or dense basicMul when the buckets are
     missing; FP16 bundle -> bucketMul.  (Q8 was abandoned in the reference: it asserts false.)"""

@@ -1283,6 +1283,16 @@ extern "C" int effort_dense_gemv(effort_ctx* c, const void* W, const float* v, f
     if (s != rocblas_status_success) return fail(c, EFFORT_ERR_BLAS, "rocblas_hssgemv_strided_batched");
     return EFFORT_OK;
 }
+// basicMul on expert *expNo of a stack of cores: always the in-tree kernel (rocBLAS takes its matrix from the host side)
+extern "C" int effort_dense_gemv_expert(effort_ctx* c, const void* W, const uint32_t* expNo, const float* v, float* out, int inDim, int outDim,
+                                        int numExperts) {
+    if (!c || !W || !expNo || !v || !out || inDim <= 0 || outDim <= 0 || numExperts <= 0) return fail(c, EFFORT_ERR_ARG, "dense_gemv_expert: bad argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    if (!dense_gemv_supported((uint32_t)inDim, (uint32_t)outDim) || (size_t)numExperts * outDim * inDim * 2 > 0xFFFFFFFFull)
+        return fail(c, EFFORT_ERR_SHAPE, "dense_gemv_expert: inDim % 16 != 0, inDim > 65536, or a stack of 4 GiB or more");
+    HIP_TRY(c, launch_dense_gemv_expert(static_cast<const uint16_t*>(W), expNo, v, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)numExperts, c->stream));
+    return EFFORT_OK;
+}
 
 // ---- converter -----------------------------------------------------------------------------------
 extern "C" int effort_convert_fp16_pitched(effort_ctx* c, const void* W, int outDim, int inDim, void* buckets, int rowPitchBytes, void* stats, void* probes) {
@@ -1395,6 +1405,22 @@ extern "C" int effort_mix2(effort_ctx* c, const float* f0, const float* f1, cons
     if (!c || !f0 || !f1 || !val2 || !out || n <= 0) return fail(c, EFFORT_ERR_ARG, "mix2: bad argument");
     { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
     HIP_TRY(c, launch_mix2(f0, f1, val2, out, (uint32_t)n, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_moe_route(effort_ctx* c, const float* h, const void* normW, const void* gateW, int n, int numExperts, float* gateOut,
+                                uint32_t* idx2, float* val2) {
+    if (!c || !h || !normW || !gateW || !idx2 || !val2) return fail(c, EFFORT_ERR_ARG, "moe_route: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    if (n <= 0 || numExperts <= 0 || !moe_route_supported((uint32_t)n, (uint32_t)numExperts))
+        return fail(c, EFFORT_ERR_SHAPE, "moe_route: n % 16 == 0, 16 <= n <= 16384, 1 <= numExperts <= 64");
+    HIP_TRY(c, launch_moe_route(h, static_cast<const uint16_t*>(normW), static_cast<const uint16_t*>(gateW), (uint32_t)n, (uint32_t)numExperts, gateOut,
+                                idx2, val2, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_mix2_add(effort_ctx* c, float* h, const float* f0, const float* f1, const float* val2, int n) {
+    if (!c || !h || !f0 || !f1 || !val2 || n <= 0) return fail(c, EFFORT_ERR_ARG, "mix2_add: bad argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_mix2_add(h, f0, f1, val2, (uint32_t)n, c->stream));
     return EFFORT_OK;
 }
 extern "C" int effort_argmax(effort_ctx* c, const float* logits, int n, uint32_t* idOut, uint32_t* pos, uint32_t* history, int historyLen) {

@@ -8,6 +8,9 @@
 //   silu_mul         x3 * x1 / (1 + exp(-x1))                              silu32b (matrix.metal:25-35)
 //   fetch_row        tok_embeddings row (f16) -> f32                       fetchRow16to32 (aux.metal:355)
 //   top2_softmax     Mixtral gate: top-2 experts + softmax of their logits (mpsTopK + softmax, runNetwork.swift:186-189); mix2: weighted sum
+//   moe_route        Mixtral routing in ONE launch: rmsNorm * ffnNorm -> dense gate GEMV -> top-2 + softmax (runNetwork.swift:173-175,185-189),
+//                    bit for bit what add_rmsnorm_mul -> dense_gemv_kernel<1, 0> -> top2_softmax write in a row
+//   mix2_add         h += f0 * val[0] + f1 * val[1]: mix2 and the residual add the next norm would have done (runNetwork.swift:190-199)
 //   argmax           greedy pick of the next token (the reference takes mpsTopK[0], helpers/mps.swift:52-84), pos += 1
 #include "effort_internal.h"
 
@@ -311,8 +314,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
 }
 
 // Mixtral routing (runNetwork.swift:185-199): mpsTopK(topK: 2) of the gate logits, softmax over the two picked values.
-__global__ void top2_softmax_kernel(const float* __restrict__ gate, uint32_t n, uint32_t* __restrict__ idx, float* __restrict__ val) {
-    if (threadIdx.x != 0) return;
+__device__ __forceinline__ void top2_softmax_scan(const float* gate, uint32_t n, uint32_t* __restrict__ idx, float* __restrict__ val) {
     uint32_t i0 = 0, i1 = 0xFFFFFFFFu; float v0 = -INFINITY, v1 = -INFINITY;
     for (uint32_t i = 0; i < n; i++) {
         const float x = gate[i];
@@ -323,11 +325,119 @@ __global__ void top2_softmax_kernel(const float* __restrict__ gate, uint32_t n, 
     const float e1 = expf(v1 - v0), inv = 1.0f / (1.0f + e1);
     idx[0] = i0; idx[1] = i1; val[0] = inv; val[1] = e1 * inv;
 }
+__global__ void top2_softmax_kernel(const float* __restrict__ gate, uint32_t n, uint32_t* __restrict__ idx, float* __restrict__ val) {
+    if (threadIdx.x != 0) return;
+    top2_softmax_scan(gate, n, idx, val);
+}
 // out = f0 * val[0] + f1 * val[1]   (ffnOut[i].mul(by: gateVals[i]); h.add(by: ffnOut[i]) -- the add rides in the next norm)
 __global__ void mix2_kernel(const float* __restrict__ f0, const float* __restrict__ f1, const float* __restrict__ val,
                             float* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = f0[i] * val[0] + f1[i] * val[1];
+}
+
+// h += f0 * val[0] + f1 * val[1]: mix2_kernel's expression, then the one f32 add the next add_rmsnorm_mul would have performed
+__global__ void mix2_add_kernel(float* __restrict__ h, const float* __restrict__ f0, const float* __restrict__ f1,
+                                const float* __restrict__ val, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) h[i] = h[i] + (f0[i] * val[0] + f1[i] * val[1]);
+}
+
+// Mixtral routing in ONE launch of one workgroup (16 waves): x = rmsNorm(h) * w -> gate[e] = gateW[e] . f16(x) -> top-2 + softmax.
+// The three kernels it replaces sit on the token's dependent chain, each a launch that reads a few KB and waits for the one before.
+// Every sum runs in THEIR order, so idx / val (and the logits) are theirs bit for bit:
+//   norm   thread t squares elements t, t + 1024, ... in that order; block_sum; (x * inv) * w      (add_rmsnorm_mul_kernel, both its paths)
+//   gate   a lane owns 8 consecutive halves of every 512-element chunk: an fmaf chain from 0 over the 8, chunk sums added to the lane's
+//          accumulator in ascending chunk order (the chunk straddling n masked per lane), the xor butterfly 32 .. 1   (dense_gemv_kernel<1, 0>)
+//   top-2  top2_softmax_scan
+// A wave owns an expert row (rows beyond 16 go round again).  The gate rows do not depend on the norm: a wave's first eight 16-byte
+// row loads per lane are asked for at entry beside h and the norm weights, so the chain is ONE memory round trip, the reduction, the
+// LDS hand-over of f16(x) and the dot products.  n % 16 == 0, 16 <= n <= kRouteMaxN, 1 <= numExperts <= kRouteMaxExperts (the launcher's caller checks).
+constexpr uint32_t kRouteMaxN = 16384, kRouteMaxExperts = 64;
+typedef _Float16 route_half2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(1024) void moe_route_kernel(const float* __restrict__ h, const uint16_t* __restrict__ w,
+                                                         const uint16_t* __restrict__ gateW, uint32_t n, uint32_t numExperts,
+                                                         float* __restrict__ gateOut, uint32_t* __restrict__ idx, float* __restrict__ val) {
+    __shared__ __attribute__((aligned(16))) uint16_t xh[kRouteMaxN];          // f16(x), padded with zeros to a multiple of 512
+    __shared__ float red[17];
+    __shared__ float logit[kRouteMaxExperts];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t padded = (n + 511u) / 512u * 512u;
+    constexpr int K = 4, U = 8;
+    // every load that depends on nothing: this wave's first row (8 chunks of 512), the first 4096 of h and of the norm weights
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(gateW), 0, (int)(numExperts * n * 2u), 0x00020000);
+    uint32_t w0[U][4];
+    {
+        const uint32_t rowOff = __builtin_amdgcn_readfirstlane(min(wave, numExperts - 1u) * n * 2u);     // (a wave without a row re-reads the last one)
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t e = min(u * 512u + lane * 8u, n - 8u);                // clamped, branch-free (n % 16 == 0)
+            const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs, e * 2u, rowOff, 0);
+            w0[u][0] = t[0]; w0[u][1] = t[1]; w0[u][2] = t[2]; w0[u][3] = t[3];
+        }
+    }
+    float x[K], wf[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t i = min(k * 1024u + tid, n - 1u);
+        x[k] = h[i];
+        wf[k] = half_bits_to_float(w[i]);
+    }
+    float ss = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; k++) ss += k * 1024u + tid < n ? x[k] * x[k] : 0.0f;
+    for (uint32_t i = K * 1024u + tid; i < n; i += 1024u) { const float y = h[i]; ss += y * y; }
+    const float inv = 1.0f / sqrtf(block_sum(ss, red) / (float)n + 1e-5f);                // aux.metal:150
+    // v.asFloat16(), mps.swift:19.  The f32 product is pinned in a register first: left to itself the compiler folds the last multiply and
+    // the conversion into ONE v_fma_mixlo_f16, which does not write the bits the GEMV's v_cvt_f16_f32 of the stored f32 value writes
+    auto h16 = [](float y) -> uint16_t { asm volatile("" : "+v"(y)); return __half_as_ushort(__float2half_rn(y)); };
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        if (k * 1024u + tid < n) xh[k * 1024u + tid] = h16((x[k] * inv) * wf[k]);
+    for (uint32_t i = K * 1024u + tid; i < n; i += 1024u) xh[i] = h16((h[i] * inv) * half_bits_to_float(w[i]));
+    for (uint32_t i = n + tid; i < padded; i += 1024u) xh[i] = 0;
+    __syncthreads();
+    for (uint32_t row = wave; row < numExperts; row += 16u) {                     // (uniform per wave)
+        const uint32_t rowOff = __builtin_amdgcn_readfirstlane(row * n * 2u);
+        float acc = 0.0f;
+        for (uint32_t c0 = 0; c0 < padded; c0 += 512u * U) {
+            uint32_t wr[U][4];
+            if (row == wave && c0 == 0u) {
+#pragma unroll
+                for (int u = 0; u < U; u++) { wr[u][0] = w0[u][0]; wr[u][1] = w0[u][1]; wr[u][2] = w0[u][2]; wr[u][3] = w0[u][3]; }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t e = min(c0 + u * 512u + lane * 8u, n - 8u);
+                    const auto t = __builtin_amdgcn_raw_buffer_load_b128(rs, e * 2u, rowOff, 0);
+                    wr[u][0] = t[0]; wr[u][1] = t[1]; wr[u][2] = t[2]; wr[u][3] = t[3];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint32_t e = c0 + u * 512u + lane * 8u;
+                const bool live = e < n;                                           // a clamped lane holds a copy of another lane's data
+                const uint4 xq = *reinterpret_cast<const uint4*>(xh + min(e, padded - 8u));
+                const uint32_t xw[4] = {xq.x, xq.y, xq.z, xq.w};
+                float a = 0.0f;
+#pragma unroll
+                for (int p = 0; p < 4; p++) {                                      // exact f16 products, f32 sums
+                    const route_half2 wh = __builtin_bit_cast(route_half2, wr[u][p]), xv = __builtin_bit_cast(route_half2, xw[p]);
+                    a = fmaf((float)wh[0], (float)xv[0], a);
+                    a = fmaf((float)wh[1], (float)xv[1], a);
+                }
+                acc += live ? a : 0.0f;                                            // (a chunk past n adds 0, as it does in the GEMV)
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+        if (lane == 0) {
+            logit[row] = acc;
+            if (gateOut) gateOut[row] = acc;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) top2_softmax_scan(logit, numExperts, idx, val);
 }
 
 hipError_t launch_top2_softmax(const float* gate, uint32_t n, uint32_t* idx, float* val, hipStream_t st) {
@@ -336,6 +446,18 @@ hipError_t launch_top2_softmax(const float* gate, uint32_t n, uint32_t* idx, flo
 }
 hipError_t launch_mix2(const float* f0, const float* f1, const float* val, float* out, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(mix2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, f0, f1, val, out, n);
+    return hipGetLastError();
+}
+hipError_t launch_mix2_add(float* h, const float* f0, const float* f1, const float* val, uint32_t n, hipStream_t st) {
+    hipLaunchKernelGGL(mix2_add_kernel, dim3((n + 255) / 256), dim3(256), 0, st, h, f0, f1, val, n);
+    return hipGetLastError();
+}
+bool moe_route_supported(uint32_t n, uint32_t numExperts) {
+    return n % 16u == 0 && n >= 16u && n <= kRouteMaxN && numExperts >= 1u && numExperts <= kRouteMaxExperts;
+}
+hipError_t launch_moe_route(const float* h, const uint16_t* w, const uint16_t* gateW, uint32_t n, uint32_t numExperts, float* gateOut,
+                            uint32_t* idx, float* val, hipStream_t st) {
+    hipLaunchKernelGGL(moe_route_kernel, dim3(1), dim3(1024), 0, st, h, w, gateW, n, numExperts, gateOut, idx, val);
     return hipGetLastError();
 }
 hipError_t launch_add_rmsnorm_mul(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, hipStream_t st) {

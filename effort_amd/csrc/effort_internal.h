@@ -207,6 +207,8 @@ inline hipError_t allow_full_lds(const void* fn) {
 // ---- launchers (one per translation unit) ---------------------------------------------------
 bool dense_gemv_supported(uint32_t inDim, uint32_t outDim);
 hipError_t launch_dense_gemv(const uint16_t* W_f16, const float* v, float* out, uint32_t inDim, uint32_t outDim, hipStream_t st);
+hipError_t launch_dense_gemv_expert(const uint16_t* W_f16, const uint32_t* expNo, const float* v, float* out, uint32_t inDim, uint32_t outDim,
+                                    uint32_t numExperts, hipStream_t st);
 hipError_t launch_find_cutoff(const float* v, const uint16_t* probes, const uint32_t* expNo, uint32_t q,
                               float* cutoff, uint32_t* dispatchCount, unsigned long long* tstamp, hipStream_t st);
 
@@ -247,6 +249,10 @@ hipError_t launch_silu_mul(const float* x1, const float* x3, float* out, uint32_
 hipError_t launch_fetch_row(const uint16_t* emb, const uint32_t* id, float* out, uint32_t n, hipStream_t st);
 hipError_t launch_top2_softmax(const float* gate, uint32_t n, uint32_t* idx, float* val, hipStream_t st);
 hipError_t launch_mix2(const float* f0, const float* f1, const float* val, float* out, uint32_t n, hipStream_t st);
+hipError_t launch_mix2_add(float* h, const float* f0, const float* f1, const float* val, uint32_t n, hipStream_t st);
+bool moe_route_supported(uint32_t n, uint32_t numExperts);
+hipError_t launch_moe_route(const float* h, const uint16_t* w, const uint16_t* gateW, uint32_t n, uint32_t numExperts, float* gateOut,
+                            uint32_t* idx, float* val, hipStream_t st);
 hipError_t launch_argmax(const float* logits, uint32_t n, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
                          int* status, hipStream_t st);
 

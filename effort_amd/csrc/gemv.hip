@@ -18,8 +18,8 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 // ROWS = rows a wave works on at once (they share the LDS reads of v): 2, or 1 when the matrix has too few rows to fill the chip
 template <int kGemvRows, int AUX>       // eight 16-byte loads in flight per lane: 8 / ROWS 1 KB chunks of each row
-__global__ __launch_bounds__(64 * kGemvWaves) void dense_gemv_kernel(const uint16_t* __restrict__ W, const float* __restrict__ v,
-                                                                     float* __restrict__ out, uint32_t inDim, uint32_t outDim) {
+__device__ __forceinline__ void dense_gemv_body(const uint16_t* __restrict__ W, const float* __restrict__ v,
+                                                float* __restrict__ out, uint32_t inDim, uint32_t outDim) {
     extern __shared__ __attribute__((aligned(16))) uint16_t vh[];              // f16(v), padded with zeros to a multiple of 512
     const uint32_t padded = (inDim + 511u) / 512u * 512u;
     auto h16 = [](float x) -> uint32_t { return __half_as_ushort(__float2half_rn(x)); };       // v.asFloat16(), mps.swift:19
@@ -91,6 +91,23 @@ __global__ __launch_bounds__(64 * kGemvWaves) void dense_gemv_kernel(const uint1
     }
 }
 
+template <int kGemvRows, int AUX>
+__global__ __launch_bounds__(64 * kGemvWaves) void dense_gemv_kernel(const uint16_t* __restrict__ W, const float* __restrict__ v,
+                                                                     float* __restrict__ out, uint32_t inDim, uint32_t outDim) {
+    dense_gemv_body<kGemvRows, AUX>(W, v, out, inDim, outDim);
+}
+// The same body on expert *expNo of a stack W [numExperts][outDim][inDim] (the dense baseline of a routed FFN: the expert number stays
+// on the device).  A kernel of its own, so that a plain dense call keeps its code: no dependent scalar load in front of its first row
+// load.  Here the expert number is asked for at entry and first needed after v has been staged in LDS.  A device value cannot be
+// refused: it is clamped to the last expert.
+template <int kGemvRows, int AUX>
+__global__ __launch_bounds__(64 * kGemvWaves) void dense_gemv_expert_kernel(const uint16_t* __restrict__ W, const uint32_t* __restrict__ expNo,
+                                                                            const float* __restrict__ v, float* __restrict__ out,
+                                                                            uint32_t inDim, uint32_t outDim, uint32_t numExperts) {
+    const uint32_t e = min(expNo[0], numExperts - 1u);
+    dense_gemv_body<kGemvRows, AUX>(W + (size_t)e * outDim * inDim, v, out, inDim, outDim);
+}
+
 // inDim % 16 == 0, inDim * 2 padded to 1 KB must fit the LDS, W below 4 GiB; otherwise the caller falls back to rocBLAS
 bool dense_gemv_supported(uint32_t inDim, uint32_t outDim) {
     return inDim % 16 == 0 && inDim >= 16 && inDim <= 65536 && (size_t)outDim * inDim * 2 <= 0xFFFFFFFFull;
@@ -112,6 +129,29 @@ hipError_t launch_dense_gemv(const uint16_t* W, const float* v, float* out, uint
     const bool nt = (size_t)inDim * outDim * 2u > kGemvKeepBytes;
     if (outDim <= 8192u) return nt ? launch_dense_gemv_t<1, 2>(W, v, out, inDim, outDim, st) : launch_dense_gemv_t<1, 0>(W, v, out, inDim, outDim, st);
     return nt ? launch_dense_gemv_t<2, 2>(W, v, out, inDim, outDim, st) : launch_dense_gemv_t<2, 0>(W, v, out, inDim, outDim, st);
+}
+
+template <int ROWS, int AUX>
+static hipError_t launch_dense_gemv_expert_t(const uint16_t* W, const uint32_t* expNo, const float* v, float* out, uint32_t inDim, uint32_t outDim,
+                                             uint32_t numExperts, hipStream_t st) {
+    const uint32_t lds = (inDim + 511u) / 512u * 512u * 2u;
+    if (lds > 48u * 1024u) {
+        hipError_t e = allow_full_lds(reinterpret_cast<const void*>(&dense_gemv_expert_kernel<ROWS, AUX>));
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t rowsPerWg = kGemvWaves * ROWS;
+    hipLaunchKernelGGL((dense_gemv_expert_kernel<ROWS, AUX>), dim3((outDim + rowsPerWg - 1) / rowsPerWg), dim3(64 * kGemvWaves), lds, st, W, expNo, v, out,
+                       inDim, outDim, numExperts);
+    return hipGetLastError();
+}
+
+// instantiation and cache policy by ONE expert's matrix, as launch_dense_gemv picks them for that matrix alone
+hipError_t launch_dense_gemv_expert(const uint16_t* W, const uint32_t* expNo, const float* v, float* out, uint32_t inDim, uint32_t outDim,
+                                    uint32_t numExperts, hipStream_t st) {
+    const bool nt = (size_t)inDim * outDim * 2u > kGemvKeepBytes;
+    if (outDim <= 8192u)
+        return nt ? launch_dense_gemv_expert_t<1, 2>(W, expNo, v, out, inDim, outDim, numExperts, st) : launch_dense_gemv_expert_t<1, 0>(W, expNo, v, out, inDim, outDim, numExperts, st);
+    return nt ? launch_dense_gemv_expert_t<2, 2>(W, expNo, v, out, inDim, outDim, numExperts, st) : launch_dense_gemv_expert_t<2, 0>(W, expNo, v, out, inDim, outDim, numExperts, st);
 }
 
 }  // namespace effort

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .bucket_mul import basicMul, bucketMul, bucketMulGroup, bucketMulQ4
+from .bucket_mul import basicMul, basicMulExpert, bucketMul, bucketMulGroup, bucketMulQ4
 from .runtime import gpu as _gpu
 from .weights import ExpertWeights
 
@@ -184,6 +184,7 @@ class Decoder:
         # Measured at Mistral-7B shapes, 25 % effort, 64 tokens (tools/bench_extra.py --sections decode_q4): 299 tokens/s with the glue
         # kernels against 281 with gate + residual folded into the Q4 w2 launch (effort_bucketmul_q4_group_fused).  Opt in with
         # fused_glue=True or a tuple of parts; the logits are the same within 2e-3 either way (bit-identical on the test model).
+        asked = fused_glue is True                        # (a Mixtral model folds only when asked: its default is decided below)
         if fused_glue is None:
             fused_glue = Q4_FUSED_DEFAULT if self.mixed else True
         # (Round 4's `chain=True` -- a layer's dependent multiplies as ONE launch of resident workgroups -- measured 252 against 308
@@ -196,8 +197,17 @@ class Decoder:
         # 50 %); the gate alone or the residuals alone still lose 1 % (tools/lab/decode_ab.py --fused-glue ...).  Bit-identical logits.
         # fused_glue may also name WHICH steps fold into the multiplies: any of "norm" (rmsNorm into wq|wk|wv and w1|w3), "gate"
         # (silu into w2), "resid" (the residual adds after wo and w2); True = all three
+        # Mixtral (a layer with an ffnGate) folds ALL OR NOTHING, and only when asked: fused_glue=True makes a layer 7 launches instead of
+        # 12 -- wq|wk|wv with the norm prologue, rope_attention, wo with the residual, effort_moe_route (norm + gate GEMV + top-2 in one
+        # launch), both experts' w1|w3 with the norm prologue, both w2 with the gate prologue, effort_mix2_add (mix + residual).  None,
+        # False or a tuple of parts keep the separate glue kernels there: the default, until tools/bench_extra.py --sections decode_mixtral
+        # (which times both in one process) has a recorded run -- there is none yet, the folded loop's speed is UNMEASURED.
         parts = ("norm", "gate", "resid") if fused_glue is True else tuple(fused_glue or ())
-        self.fuse = frozenset(parts) if all(L.ffnGate is None for L in model.layers) else frozenset()
+        self.moe = any(L.ffnGate is not None for L in model.layers)
+        if self.moe:
+            self.fuse = frozenset(parts) if asked and all(L.ffnGate is not None for L in model.layers) else frozenset()
+        else:
+            self.fuse = frozenset(parts)
         self.fused_glue = bool(self.fuse)
         self.model, self.maxTokens = model, int(maxTokens)
         dev = model.norm.device
@@ -212,7 +222,7 @@ class Decoder:
         self.sharded = bool(sharded) if sharded is not None else (self.world > 1)
         self.groups = None
         if self.sharded or emulate_world:
-            if self.fuse != {"norm", "gate", "resid"}:
+            if self.moe or self.fuse != {"norm", "gate", "resid"}:
                 raise ValueError("the column-sharded decode loop needs the glue folded into the multiplies (fused_glue=True, dense FFN)")
             if not emulate_world and not self.g.has_comm:
                 raise RuntimeError("Decoder(sharded=True): give the device's context its communicator first (effort_amd.sharded.init_comm / Gpu.comm_create)")
@@ -239,6 +249,7 @@ class Decoder:
         self.tokId = torch.zeros(1, dtype=torch.int32, device=dev)
         self.history = torch.zeros(self.maxTokens, dtype=torch.int32, device=dev)
         self._graphs: dict = {}
+        self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
     def token_step(self, effort: float = 0.25, dense: bool = False):
@@ -272,6 +283,29 @@ class Decoder:
                 G.mul(self.x1, [(L.w2, self.h, {"gate": self.x3, "resid": self.h})], effort)                             # :181-183, in place on h
             ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
             basicMul(self.outNormed, m.output, self.logits)                                           # :222 (replicated: every rank picks the same token)
+            ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+            return
+        if self.fused_glue and self.moe and not dense:
+            # Mixtral, everything folded: 7 launches per layer.  The routing reads h and ffnNorm itself, the experts' w1|w3 take the
+            # same norm as their prologue (the same bits: both sum in add_rmsnorm_mul_kernel's order), and the mix lands on h.
+            e0, e1 = self.gateIdxs[0:1], self.gateIdxs[1:2]
+            for n, L in enumerate(m.layers):
+                an, fnw = {"norm": L.attnNorm}, {"norm": L.ffnNorm}
+                bucketMulGroup([(self.h, L.wq, None, self.xq_temp, effort, an), (self.h, L.wk, None, self.xk_temp, effort, an),
+                                (self.h, L.wv, None, self.xv_temp, effort, an)])                                       # :121-134
+                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
+                                             _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
+                                             C.c_float(cfg.ropeBase)), "rope_attention")
+                bucketMulGroup([(self.attnOutput, L.wo, None, self.h, effort, {"resid": self.h})])                   # :170-172, h += wo(attn)
+                ck(lib.effort_moe_route(g.ctx, _p(self.h), _p(L.ffnNorm), _p(L.ffnGate), cfg.stateDim, cfg.numExperts, None,
+                                        _p(self.gateIdxs), _p(self.gateVals)), "moe_route")                         # :173-175,185-189
+                bucketMulGroup([(self.h, L.w1, e0, self.x1, effort, fnw), (self.h, L.w3, e0, self.x3, effort, fnw),
+                                (self.h, L.w1, e1, self.x1b, effort, fnw), (self.h, L.w3, e1, self.x3b, effort, fnw)])
+                bucketMulGroup([(self.x1, L.w2, e0, self.ffnOut, effort, {"gate": self.x3}),
+                                (self.x1b, L.w2, e1, self.ffnOutB, effort, {"gate": self.x3b})])
+                ck(lib.effort_mix2_add(g.ctx, _p(self.h), _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), cfg.stateDim), "mix2_add")   # :190-199
+            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
+            basicMul(self.outNormed, m.output, self.logits)                                           # :222
             ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
             return
         if self.fused_glue and not dense:
@@ -422,14 +456,28 @@ class Decoder:
         ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
 
     def _dense_experts(self, L, e0, e1):
-        """Dense baseline of the routed FFN: the picked experts' cores are gathered on the device (index_select keeps the
-        step graph-capturable), then plain basicMul."""
+        """Dense baseline of the routed FFN: basicMul on the picked expert of each stack of cores, the expert number read on the device
+        (basicMulExpert: nothing is gathered).  Under the rocBLAS dense backend, or for a stack the package's kernel does not serve, the
+        picked cores are gathered on the device first (index_select keeps the step graph-capturable: three whole matrices copied per
+        expert), then plain basicMul."""
         cfg, g, lib = self.cfg, self.g, _lib.lib()
+
+        def mul(v, cores, e, out):
+            if not g.dense_rocblas:
+                try:
+                    basicMulExpert(v, cores, e, out)
+                    self.dense_expert_gemv = True
+                    return
+                except _lib.EffortError as ex:
+                    if ex.code != -2:                      # EFFORT_ERR_SHAPE: the library's own word on what its kernel serves (nothing was enqueued)
+                        raise
+            self.dense_expert_gemv = False
+            basicMul(v, torch.index_select(cores, 0, e)[0], out)
         for e, x1, x3, x2, out in ((e0, self.x1, self.x3, self.x2, self.ffnOut), (e1, self.x1b, self.x3b, self.x2b, self.ffnOutB)):
-            basicMul(self.fxn, torch.index_select(L.w1.core, 0, e)[0], x1)
-            basicMul(self.fxn, torch.index_select(L.w3.core, 0, e)[0], x3)
+            mul(self.fxn, L.w1.core, e, x1)
+            mul(self.fxn, L.w3.core, e, x3)
             g.check(lib.effort_silu_mul(g.ctx, _p(x1), _p(x3), _p(x2), cfg.hiddenDim), "silu")
-            basicMul(x2, torch.index_select(L.w2.core, 0, e)[0], out)
+            mul(x2, L.w2.core, e, out)
 
     def _graph(self, effort: float, dense: bool):
         key = ("dense",) if dense else (float(effort),)

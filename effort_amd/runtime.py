@@ -24,6 +24,7 @@ class Gpu:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             self.ctx = self._lib.effort_create(self.device, C.c_void_p(stream))
         self.has_comm = False
+        self.dense_rocblas = False                         # what set_dense_backend last chose
         if not self.ctx:
             raise RuntimeError("effort_create failed: " + (self._lib.effort_last_error(None) or b"").decode())
         self._stream = stream
@@ -142,6 +143,7 @@ class Gpu:
     def set_dense_backend(self, rocblas: bool = False):
         """basicMul through the library's hssgemv (True) or the streaming HIP kernel (False, default)."""
         self.check(self._lib.effort_set_dense_backend(self.ctx, int(bool(rocblas))), "set_dense_backend")
+        self.dense_rocblas = bool(rocblas)
 
     def convert_status(self) -> int:
         """Elements the bucketize() calls since the last query could not place (effort_convert_status); reads and clears."""

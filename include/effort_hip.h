@@ -189,6 +189,14 @@ EFFORT_API int effort_bucketmul_q4(effort_ctx* ctx, const effort_w* w, const flo
 EFFORT_API int effort_dense_gemv(effort_ctx* ctx, const void* W_f16_dev, const float* v_dev, float* out_dev,
                       int inDim, int outDim);
 EFFORT_API int effort_set_dense_backend(effort_ctx* ctx, int rocblas);
+/* basicMul on ONE expert of a stack of cores, W f16 [numExperts][outDim][inDim], the expert number read from device memory
+ * (*expNo_dev, as the multiplies take it): the dense baseline of a routed FFN without gathering the expert's matrix first.  The
+ * same kernel body and summation order as effort_dense_gemv on W[*expNo_dev], hence its result bit for bit; instantiation and
+ * cache policy follow the size of one expert's matrix.  Always the in-tree kernel, whatever effort_set_dense_backend says:
+ * EFFORT_ERR_SHAPE where that kernel does not serve the shape (inDim % 16, inDim > 65536) or the whole stack reaches 4 GiB.
+ * A device value cannot be refused by a return code: an expert number >= numExperts is CLAMPED to numExperts - 1. */
+EFFORT_API int effort_dense_gemv_expert(effort_ctx* ctx, const void* W_f16_dev, const uint32_t* expNo_dev, const float* v_dev,
+                             float* out_dev, int inDim, int outDim, int numExperts);
 
 /* A GROUP of n (1..32) independent bucketMul calls in ONE kernel launch: call i multiplies vs[i] by ws[i] at
  * efforts[i] into outs[i] (expNos may be NULL, or hold NULL entries = expert 0).  Same row selection as n
@@ -302,6 +310,18 @@ EFFORT_API int effort_fetch_row(effort_ctx* ctx, const void* emb_f16_dev, const 
  * val2_dev = softmax over those two logits; effort_mix2: out = f0 * val2[0] + f1 * val2[1]. */
 EFFORT_API int effort_top2_softmax(effort_ctx* ctx, const float* gate_dev, int n, uint32_t* idx2_dev, float* val2_dev);
 EFFORT_API int effort_mix2(effort_ctx* ctx, const float* f0_dev, const float* f1_dev, const float* val2_dev, float* out_dev, int n);
+/* Mixtral routing in ONE launch (runNetwork.swift:173-175,185-189): x = h / sqrt(mean(h^2) + 1e-5) * norm_w; gate[e] = sum f16(x) * gate[e][.]
+ * (exact f16 products, f32 sums; gate f16 [numExperts][n]); idx2_dev = the two largest logits' experts (strict >, lowest index first; with
+ * numExperts == 1 expert 0 is picked twice with the weights 1.0 / 0.0, as effort_top2_softmax writes them), val2_dev = softmax over
+ * those two.  Bit for bit what effort_add_rmsnorm_mul(h, NULL, norm_w, x) ->
+ * effort_dense_gemv(gate, x, logits) on the in-tree kernel -> effort_top2_softmax write in a row; h is not modified.  gate_out_dev
+ * (may be NULL) receives the numExperts logits, for tests and debugging.  n % 16 == 0, 16 <= n <= 16384, 1 <= numExperts <= 64;
+ * anything else returns EFFORT_ERR_SHAPE with nothing enqueued. */
+EFFORT_API int effort_moe_route(effort_ctx* ctx, const float* h_dev, const void* norm_w_f16_dev, const void* gate_f16_dev, int n, int numExperts,
+                     float* gate_out_dev, uint32_t* idx2_dev, float* val2_dev);
+/* h[i] = h[i] + (f0[i] * val2[0] + f1[i] * val2[1]): effort_mix2 and the residual add of the following effort_add_rmsnorm_mul in one
+ * launch, bit for bit (runNetwork.swift:190-199). */
+EFFORT_API int effort_mix2_add(effort_ctx* ctx, float* h_dev, const float* f0_dev, const float* f1_dev, const float* val2_dev, int n);
 /* greedy pick: *id_out_dev = argmax(logits) (the reference takes mpsTopK[0], helpers/mps.swift:52-84); if history_dev is
  * given, history_dev[*pos_dev] = the pick; then *pos_dev += 1. */
 EFFORT_API int effort_argmax(effort_ctx* ctx, const float* logits_dev, int n, uint32_t* id_out_dev, uint32_t* pos_dev, uint32_t* history_dev,

@@ -2,8 +2,9 @@
 """tools/bench_extra.py -- the sections round 5's bench.py carried behind the headline and the driver's one command no longer runs
 (VERDICT r05 item 7): `by_streams`, `shared_matrices`, `four_contexts`, the timeit-protocol variants, the quality sweeps
 (heavy-tailed input, a structured matrix, the structured decode model), the other shapes, `shard_projection` (BASELINE config 4's
-column split projected on one GPU), the one-GPU `layer_latency` (a world of one through RCCL + projected ranks) and `decode_q4` (the
-decode loop on the reference's Q4 model beside the FP16 one).
+column split projected on one GPU), the one-GPU `layer_latency` (a world of one through RCCL + projected ranks), `decode_q4` (the
+decode loop on the reference's Q4 model beside the FP16 one) and `decode_mixtral` (the routed decode loop at Mixtral-8x7B shapes: dense,
+and effort with the glue kernels separate or folded; its record also goes to profiles/r07_decode_mixtral.json).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -20,7 +21,7 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency", "decode_q4")
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral")
 
 
 def by_streams(b, res):
@@ -262,6 +263,52 @@ def decode_q4(b, res):
     del model
 
 
+def decode_mixtral(b, res):
+    """The routed decode loop at Mixtral-8x7B shapes (state 4096, hidden 14336, 8 experts, 32 / 8 heads), structured weights, 8 LAYERS
+    (buckets + cores of 8 layers are about 45 GB), 64 tokens: ms per token and us per layer for the dense baseline (the picked experts'
+    cores through effort_dense_gemv_expert, nothing gathered), effort 25 % with the separate glue kernels (12 launches per layer),
+    25 % folded (Decoder(fused_glue=True): 7 launches) and 50 % folded.  Fused and unfused run in this one process, one after the other."""
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    b.g.set_tuning(0, 0, 0)
+    b.g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    prompt, nt, layers = [1, 733, 16289, 28793, 22557], 64, 8
+    cfg = MistralConfig(numLayers=layers, numExperts=8)
+    model = Model.random(cfg, seed=1, structured=True)
+
+    def timed(dec, **kw):
+        best, ids = float("inf"), None
+        for _ in range(3):
+            ids, dt, _ = dec.run(prompt, nt, **kw)
+            best = min(best, dt)
+        return {"ms_per_token": round(best * 1e3, 4), "us_per_layer": round(best * 1e6 / layers, 2)}, ids
+    out = {"model": "Mixtral-8x7B shapes (4096 / 14336, 8 experts, top-2, 32 / 8 heads), 8 layers, STRUCTURED random weights, seed 1", "tokens": nt,
+           "layers": layers, "protocol": "best of 3 runs of 64 tokens, hipGraph replay, timed from the 3rd step; us_per_layer = time per token / 8 "
+                                         "(the embedding fetch, the output norm, the LM head and the argmax are in it)",
+           "launches_per_layer": {"unfused": 12, "fused": 7}}
+    plain = Decoder(model, maxTokens=nt + 8)
+    folded = Decoder(model, maxTokens=nt + 8, fused_glue=True)
+    assert folded.fused_glue and not plain.fused_glue
+    B._GRAPHS_FOR_LIFE.append(plain._graphs)
+    B._GRAPHS_FOR_LIFE.append(folded._graphs)
+    out["dense_expert_gemv"], _ = timed(plain, dense=True)
+    out["effort_0.25_unfused"], ids_u = timed(plain, effort=0.25)
+    out["effort_0.25_fused"], ids_f = timed(folded, effort=0.25)
+    out["effort_0.25_unfused_again"], _ = timed(plain, effort=0.25)          # (the order of the two is not what separates them)
+    out["effort_0.5_fused"], _ = timed(folded, effort=0.5)
+    out["effort_0.5_unfused"], _ = timed(plain, effort=0.5)
+    out["fused_picks_the_unfused_tokens"] = ids_u == ids_f
+    out["fused_over_unfused_0.25"] = round(out["effort_0.25_unfused"]["ms_per_token"] / out["effort_0.25_fused"]["ms_per_token"], 4)
+    out["default"] = "unfused (Decoder(mixtral_model).fused_glue is False); fused_glue=True opts in"
+    res["decode_mixtral"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r07_decode_mixtral.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del plain, folded, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -276,7 +323,8 @@ def layer_latency(b, res):
 
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
-       "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4}
+       "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
+       "decode_mixtral": decode_mixtral}
 
 
 def main():

@@ -15,6 +15,7 @@
 #include "../../include/effort_hip.h"
 #include "../../include/effort_hip_debug.h"
 #include "effort_internal.h"
+#include "plan.h"
 
 using namespace effort;
 
@@ -62,6 +63,7 @@ struct effort_ctx {
     int* d_status = nullptr;
     int persistent = -1;              // workgroups per CU of group launches: -1 heuristic, 0 plain grid, R > 0 persistent
     static constexpr uint32_t kMaxTiles = 1024, kMaxSlices = 4096;
+    static constexpr size_t kSlabBytes = (size_t)64 << 20;   // a lane's partial-tile scratch
     static constexpr size_t kMaxRanges = 1024;   // address ranges a lane records between joins (do_group)
     unsigned long long* d_tstamp = nullptr;   // device-clock stamps of the multiply kernel (timing mode)
     double wallClockKHz = 100000.0;
@@ -72,9 +74,6 @@ struct effort_ctx {
     // tuning overrides (0 = heuristic)
     int tuneW = 0, tuneE = 0, tuneS = 0;
     bool splitCutoff = false;     // run findCutoff32 as its own 1-workgroup kernel instead of inside every workgroup
-    mutable bool thinEffort = false;   // the launch being cut streams next to nothing (mean effort under 8 %): the rules that RAISE the slice count of a group stand down
-                                       // (do_group sets it before the geometry is chosen; at 2 % effort 3 / 6 / 8 calls of 4096x11008 at 13 / 13 / 10 slices are 9 / 14 / 10 % SLOWER
-                                       // than at 8 -- more slabs and heads, nothing to stream -- where at 10 % they are 6 / 5 / 0 % faster and at 100 % 28 / 28 / 6 %)
     bool rowReuse = false;        // effort_set_row_reuse: the bucket-row stream with the ordinary cache policy instead of nt (GroupKArgs::split bit 3)
     // optional per-kernel timing
     bool timing = false;          // HIP events around each kernel
@@ -212,7 +211,7 @@ extern "C" effort_ctx* effort_create(int device, void* stream) {
     c->stream = reinterpret_cast<hipStream_t>(stream);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->numCU = prop.multiProcessorCount;
-    c->slabBytes = (size_t)64 << 20;
+    c->slabBytes = effort_ctx::kSlabBytes;
     {   // function attributes belong to a device: set them when the device's first context is created
         static std::mutex m; static std::map<int, bool> prepared;
         std::lock_guard<std::mutex> lk(m);
@@ -292,6 +291,118 @@ static int join_lanes(effort_ctx* c) {
 static bool overlaps(const std::vector<Lane::Range>& a, const std::vector<Lane::Range>& b) {
     for (const auto& x : a) for (const auto& y : b) if (x.lo < y.hi && y.lo < x.hi) return true;
     return false;
+}
+// ---- which lane a group launch goes to (overlap mode) ----
+// The launch may run beside the launches in flight on the OTHER lanes unless it reads or
+// writes what one of them writes, or writes what one of them reads; then it waits for that lane (or simply joins it: a
+// lane's stream is in order).  Always ordered after everything enqueued on the context's stream before this call.
+// The lane is CHOSEN first (choose_lane) and forked (made to wait, fork_lane) only when the first kernel of the group is about to be launched:
+// a group that fails validation or finds no launch geometry has then touched no stream.  From the fork on, every way out
+// records the lane's `done` event and marks the lane pending (LaneGuard), so a later join -- in particular the join a
+// caller owes the capturing stream before it ends a hipGraph capture -- always rejoins a lane that was forked.
+struct LaneChoice {
+    bool laned = false;               // the launch goes to a lane's own stream (lanes > 1 and no timing / clock mode)
+    int li = 0;
+    std::vector<Lane::Range> rd, wr;  // what the launch reads / writes
+    int hazard[effort_ctx::kMaxLanes], nh = 0;        // the lanes it must follow
+    unsigned long long capNow = 0;
+};
+struct LaneGuard {                                 // (see above)
+    Lane& L; bool forked = false;
+    ~LaneGuard() { if (forked) { L.dirty = true; L.pending = true; } }     // (the event itself: lane_mark, when somebody waits for the lane)
+};
+static int choose_lane(effort_ctx* c, LaneChoice& lc, int n, const effort_w* const* ws, const float* const* vs, const uint32_t* const* expNos,
+                       float* const* outs, const void* const* vAux, const float* const* resids) {
+    if (lc.laned) {
+        lc.capNow = capture_of(c->stream);
+        if (!lanes_match_capture(c, lc.capNow)) return EFFORT_ERR_ARG;
+        // bounded bookkeeping: a caller may enqueue arbitrarily many multiplies between joins (helpers/gpu.swift:109-119: one
+        // eval() per token); once a lane has recorded kMaxRanges ranges the lanes are JOINED -- the context's stream waits for
+        // all of them, and every later launch forks from that stream -- never forgotten
+        bool full = false;
+        for (int i = 0; i < c->nLanes; i++) full = full || c->lane[i].reads.size() + c->lane[i].writes.size() > effort_ctx::kMaxRanges;
+        if (full) { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+        auto add = [](std::vector<Lane::Range>& v, const void* p, size_t bytes) { if (p && bytes) v.push_back({(uintptr_t)p, (uintptr_t)p + bytes}); };
+        for (int i = 0; i < n; i++) {
+            add(lc.rd, vs[i], (size_t)ws[i]->inDim * 4);
+            if (expNos && expNos[i]) add(lc.rd, expNos[i], 4);
+            if (vAux && vAux[i]) add(lc.rd, vAux[i], (size_t)ws[i]->inDim * 4);
+            if (resids && resids[i]) add(lc.rd, resids[i], (size_t)ws[i]->outDim * 4);
+            add(lc.wr, outs[i], (size_t)ws[i]->outDim * 4);
+        }
+        for (int i = 0; i < c->nLanes; i++) {
+            const Lane& L = c->lane[i];
+            if (L.pending && (overlaps(lc.rd, L.writes) || overlaps(lc.wr, L.writes) || overlaps(lc.wr, L.reads))) lc.hazard[lc.nh++] = i;
+        }
+        lc.li = lc.nh ? lc.hazard[0] : c->nextLane;
+        // A chain of dependent launches lives on ONE lane and forks from the context's stream only when that stream is busy
+        // (fork_lane).  HIP multiplexes streams over a few hardware queues, and a lane that happens to share its queue with the
+        // context's stream makes hipStreamQuery(context's stream) say "busy" while the LANE works: every link of the chain then
+        // pays the event-record-and-wait fork, +8 us per call (tools/lab/lane_probe.py with EXTRA_CONTEXTS=1: one lane of four;
+        // round 5's bench record showed it at three of five efforts).  Four busy answers in a row on a pure chain: the chain MOVES
+        // to an idle lane -- one cross-lane edge, the ordinary hazard wait below -- where the stream's answer is its own again.
+        // Once between joins: if the busy answers were true (the caller really enqueues between the calls) nothing is lost but that edge.
+        if (lc.nh == 1 && c->busyStreak >= 4 && !c->migrated) {
+            for (int k = 1; k < c->nLanes; k++) {
+                const int cand = (lc.hazard[0] + k) % c->nLanes;
+                if (!c->lane[cand].pending) { lc.li = cand; c->migrated = true; c->busyStreak = 0; break; }
+            }
+        }
+    } else if (c->nLanes > 1) {
+        { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }        // timing modes: one launch at a time, on lane 0
+    }
+    return EFFORT_OK;
+}
+// Before the group's first launch.
+static int fork_lane(effort_ctx* c, const LaneChoice& lc, LaneGuard& guard) {
+    if (!lc.laned || guard.forked) return EFFORT_OK;
+    Lane& L = guard.L;
+    const int li = lc.li, nh = lc.nh;
+    const int* hazard = lc.hazard;
+    // "after everything enqueued on the context's stream before this call": an event recorded there, the lane waits -- UNLESS the
+    // stream is idle: then everything enqueued on it has completed and there is nothing to wait for.  That is the state of a
+    // caller who enqueues multiply after multiply and evaluates once (helpers/gpu.swift:109-119; the reference's own timing
+    // loop, benchmarks/benchmark.swift:245-257): all its work sits on the lanes, and the two HIP calls plus the cross-stream
+    // edge per call made that loop 45 % SLOWER with lanes than without (round 4: 32.5 against 22.5 us per call).  A capturing
+    // stream cannot be queried (and "idle" means nothing inside a capture): there the fork is a graph edge, as before.
+    bool wait = true;
+    if (lc.capNow == 0) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess) wait = false;
+        else {
+            (void)hipGetLastError();                    // ("not ready" must not linger as the thread's last error: the launchers read it after their kernels)
+            if (q != hipErrorNotReady) return fail(c, EFFORT_ERR_HIP, "hipStreamQuery", q);
+        }
+    }
+    if (wait) {
+        HIP_TRY(c, hipEventRecord(c->forkEv, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(L.own, c->forkEv, 0));
+    }
+    c->busyStreak = (wait && nh == 1 && hazard[0] == li) ? c->busyStreak + 1 : 0;     // (a dependent chain's link that had to fork)
+    guard.forked = true;
+    L.capId = lc.capNow;
+    // (a range the lane holds already is not recorded twice: a loop that multiplies into the same vectors over and over --
+    //  the reference's timing loop -- would otherwise grow the lists to their cap, and every call scan thousands of ranges)
+    auto add_new = [](std::vector<Lane::Range>& have, const std::vector<Lane::Range>& more) {
+        for (const auto& x : more) {
+            bool seen = false;
+            for (const auto& y : have) if (y.lo == x.lo && y.hi == x.hi) { seen = true; break; }
+            if (!seen) have.push_back(x);
+        }
+    };
+    // a lane this launch waits for: from here on this lane's order covers everything that lane has enqueued, so its ranges move
+    // here and it is no longer pending (a join need not wait for it, a later launch that touches those ranges follows THIS lane)
+    for (int k = 0; k < nh; k++) if (hazard[k] != li) {
+        Lane& H = c->lane[hazard[k]];
+        HIP_TRY(c, lane_mark(H));
+        HIP_TRY(c, hipStreamWaitEvent(L.own, H.done, 0));
+        add_new(L.reads, H.reads); add_new(L.writes, H.writes);
+        H.reads.clear(); H.writes.clear(); H.pending = false;
+    }
+    if (!nh) c->nextLane = (c->nextLane + 1) % c->nLanes;
+    add_new(L.reads, lc.rd);
+    add_new(L.writes, lc.wr);
+    return EFFORT_OK;
 }
 
 extern "C" int effort_set_overlap(effort_ctx* c, int lanes) {
@@ -608,244 +719,6 @@ extern "C" int effort_allgather_outputs(effort_ctx* c, const float* send, float*
     return EFFORT_OK;
 }
 
-// ---- launch geometry ----------------------------------------------------------------------------
-static bool supported(int W, int E) {
-    // must match EFFORT_GEOMS in bucket_mul.hip
-    return (W == 16 && (E == 1 || E == 2 || E == 4)) || (W == 8 && (E == 1 || E == 2 || E == 4)) ||
-           (W == 4 && (E == 1 || E == 2 || E == 4)) || (W == 2 && E == 4);
-}
-
-// Row slices per call when the launch carries `groupSize` calls and a lane owns E columns.  Measured on MI355X
-// (tools/lab/tune.py, 4096x4096 .. 14336x4096, 10-100 % effort): a workgroup's life is mostly fixed-latency steps (staging,
-// cutoff, selection, hand-off), so FEWER, fatter items win even when they leave CUs idle -- about 3/4 of an item per CU
-// for small groups, with slices between 128 and 512 input rows; from 8 calls on, the fattest slices (512 rows).
-// Q4 groups of about 10 to 16 calls on a context WITHOUT lanes (one launch on the chip at a time): the launch as ONE round of workgroups -- just
-// under two items per CU -- of 64-column tiles and tall slices.  A Q4 item's stream is bound by its CU's LDS atomic pipe, a CU's two workgroups
-// run their heads, streams and tails in step (profiles/r06_q4_timelines.txt), and what a launch then costs is one head + the CU's share of the
-// atomics + one tail: the unbalanced 384 items of the general rule (E = 2, 8 slices: half the CUs two items, half one) 65.4 us per 16-call
-// launch, 480 items (E = 1, 5 slices) 58.3; 12 calls: 57.1 -> 50.2 at 6 slices (profiles/r06_q4_one_round_sweep.txt).  With several launches in
-// flight the other launches fill the idle CUs anyway and the tall items only delay them (four in flight: 45.9 against 40.6 us): lanes keep the
-// general rule.  Returns the slices per call, or 0 when the rule does not apply (the slices would be taller than two workgroups' LDS allows).
-static uint32_t q4_one_round(const effort_ctx* c, uint32_t inDim, uint32_t groupTiles1) {
-    if (c->nLanes > 1 || c->tuneS || !groupTiles1) return 0;
-    const uint32_t sMin = (inDim + 831u) / 832u;                  // <= 832 rows per slice: 6656 candidate slots, ~78 KB of LDS, two workgroups per CU
-    const uint32_t S = (uint32_t)c->numCU * 15u / 8u / groupTiles1;      // 480 items on 256 CUs
-    return S >= sMin && S >= 2u ? S : 0u;
-}
-// Q4 groups of 3 .. 9 calls on a context without lanes: ONE item per CU -- the tallest slices (>= the slices a workgroup's LDS allows) whose items, counted on the
-// padded ranges the XCDs are dealt from (a call's range is a multiple of 8; item % 8 is the XCD), still number at most the CUs.  A launch of one round lasts as long
-// as its tallest item, and the first item past one per CU shares its CU for the whole launch: 3 calls of 4096x11008 at 8 slices (144 items of 512 rows) 30.2 us,
-// 12 slices (216 of 342) 26.2, 14 slices (252 items, 264 padded) 30.9; 6 calls at 8 slices (288 items) 40.1, at 6 (240 padded) 35.5; 8 calls at E = 2 x 8 (192 fat items)
-// 43.7, at E = 1 x 5 (256 padded) 39.5; 8 calls of 4096x4096 at E = 2 x 8 (64 items!) 42.5, at E = 1 x 16 (256) 24.8; 5 x (14336 -> 4096) at 32 slices (320 items) 56.5,
-// at 24 (240) 37.9 (round 6, third session, profiles/r06_one_round_groups.txt).  Returns the slices per call, or 0 when such a round does not exist.
-static uint32_t q4_one_per_cu(const effort_ctx* c, uint32_t inDim, uint32_t tiles1, int n, uint32_t groupTiles1) {
-    if (c->nLanes > 1 || c->tuneS || n < 3 || n > 9) return 0;
-    const uint32_t sMin = (inDim + 831u) / 832u, hi = ((inDim + 127u) / 128u + 7u) / 8u * 8u;
-    const bool same = !groupTiles1 || groupTiles1 == (uint32_t)n * tiles1;          // (a mixed group: every call's padding bounded by 7)
-    auto fits = [&](uint32_t s) {
-        return same ? (uint32_t)n * ((tiles1 * s + 7u) / 8u * 8u) <= (uint32_t)c->numCU : groupTiles1 * s + 7u * (uint32_t)n <= (uint32_t)c->numCU;
-    };
-    uint32_t S = sMin > 2u ? sMin : 2u;
-    if (!fits(S)) return 0;
-    const uint32_t top = c->thinEffort ? ((inDim + 511u) / 512u + 7u) / 8u * 8u : hi;      // (next to nothing to stream: no more slices than the small groups' minimum)
-    while (S < top && S < hi && fits(S + 1u)) S++;
-    return S;
-}
-static uint32_t pick_slices(const effort_ctx* c, const effort_w* w, int groupSize, int E, uint32_t groupTiles = 0, bool fill = true) {
-    const uint32_t tiles = (w->cols + 64 * E - 1) / (64 * E);
-    const uint32_t lo = ((w->inDim + 511) / 512 + 7) / 8 * 8, hi = ((w->inDim + 127) / 128 + 7) / 8 * 8;
-    if (w->fmt != kFp16 && (E == 1 || groupSize >= 8) && fill) {       // (8 / 9 calls that do not fit one E = 1 item per CU run at E = 2: one of THOSE per CU then -- 9 x (14336 ->
-        const uint32_t S = q4_one_per_cu(c, w->inDim, tiles, groupSize, groupTiles);     //  4096): 32 slices = 288 items 78.4 us, 24 = 216 items 56.1; 9 x (4096 -> 14336): 8 slices 64.4, 6: 54.8)
-        if (S) return S;
-    }
-    if (w->fmt != kFp16 && E == 1 && groupSize >= 8 && groupTiles) {       // (pick_elems chose E = 1 for this Q4 group: q4_one_round)
-        const uint32_t S = q4_one_round(c, w->inDim, groupTiles);
-        if (S) return S;
-    }
-    // Groups of >= 8 calls: the fewest slices (fat items: less fixed work per byte) -- unless the launch then leaves CUs WITHOUT an item: 8 calls on 4096x4096
-    // matrices are 8 x 2 tiles x 8 slices = 128 items on 256 CUs.  FP16 groups then take the small groups' rule below (about 3/4 of an item per CU; it
-    // never goes under `lo`): 8 x 4096x4096 31.8 -> 24.8 us per launch at 16 slices (32 slices: 28.7; E = 1 x 16: 27.6; E = 4 x 32: 29.7 -- round 6, third
-    // session, profiles/r06_small_matrix_groups.txt).  `fill` = false: the count pick_elems prices its choice of E with (unchanged: E is chosen as before).
-    if (groupSize >= 8 && (w->fmt != kFp16 || !fill || c->nLanes > 1 || c->thinEffort)) return lo;     // (with launches in flight on lanes the other launches fill the idle CUs: fat items stay -- 8 x 4096x4096, four in flight: 14.7 us per launch at 8 slices, 15.7 at 16)
-    // (64-column tiles -- narrow matrices, see pick_elems -- are worked best at one item per CU: measured, 14336 -> 4096 lone, 64 slices
-    //  26.9 us against 29.2 at 48)
-    // (Q4 small groups are worked at E = 1 whatever the shape and want the 3/4 too -- round 6, a pair of 4096x11008 calls: 16 slices = 192 items 23.2 us
-    //  against 25.4 at the 24 the full-CU target gave; lone and four per launch land on 192 items either way)
-    const uint32_t target = (E == 1 && w->fmt == kFp16) ? (uint32_t)c->numCU : (uint32_t)c->numCU * 3u / 4u;
-    // the launch's items come from ALL its calls: with the column tiles of the whole group known (Wq | Wk | Wv: 4 + 1 + 1 at
-    // E = 1) every call takes target / tiles slices; without, the calls are taken as equals
-    const uint32_t allTiles = groupTiles ? groupTiles : (uint32_t)groupSize * tiles;
-    uint32_t S = (target / allTiles + 4u) / 8u * 8u;       // nearest multiple of 8
-    if (S < lo) S = lo;
-    if (S > hi) S = hi;
-    // A slice's candidate slots are laid out per rank in blocks of 2^ceil(log2(rows)): a row count that is not a power of two wastes the
-    // rest of the block in staging, selection and LDS (24 slices of a 4096-row input: 171 rows in blocks of 256, a third of the slots
-    // empty).  With a power-of-two input the count snaps to the next power of two when the bounds allow.  Round 6 re-sweep of the decode
-    // loop's launches and the lone FFN shapes (tools/lab/geosweep.py, profiles/r06_geosweep.txt): every launch was within 0.3 % of its best
-    // geometry except the lone 4096 -> 14336 call -- the shape of the reference's own timing loop (benchmarks/benchmark.swift:245-257) --
-    // where the rule above gave 24 slices: 20.0 -> 18.6 us at 25 % effort, 25.4 -> 23.4 at 50 %.
-    if ((w->inDim & (w->inDim - 1u)) == 0u && (S & (S - 1u)) != 0u) {
-        uint32_t up = 8u;
-        while (up < S) up <<= 1;
-        S = up <= hi ? up : up >> 1;
-    }
-    // Groups of >= 3 FP16 calls that fit ONE round of CUs: as many slices as keep the launch at one item per CU, any count, instead of the nearest power of two
-    // under 3/4 of the CUs.  A launch of one round lasts as long as its tallest item: 3 calls of 4096x11008 at 8 slices are 144 items of 512 rows, at 13 slices
-    // 234 of 316 (30.7 -> 25.3 us per launch).  "One item per CU" is counted the way the items are DEALT: a call's item range is padded to a multiple of 8 and item
-    // % 8 is the XCD, so each call puts ceil(items / 8) on XCD 0 -- 7 calls of 33 items are 231 items but 35 on XCD 0's 32 CUs, and the launch takes 69 us
-    // where 30 items per call take 45 (round 6, third session, profiles/r06_one_round_groups.txt).  Lone calls and pairs -- the decode loop's launches,
-    // re-swept in round 6 -- keep the rule above.
-    if (w->fmt == kFp16 && fill && groupSize >= 3 && c->nLanes <= 1) {          // (four launches in flight: 3 calls of 4096x11008 13.4 us per launch at 8 slices, 15.0 at 13)
-        const bool same = allTiles == (uint32_t)groupSize * tiles;          // (a mixed group: every call's padding bounded by 7)
-        auto fits = [&](uint32_t s) {
-            return same ? (uint32_t)groupSize * ((tiles * s + 7u) / 8u * 8u) <= (uint32_t)c->numCU : allTiles * s + 7u * (uint32_t)groupSize <= (uint32_t)c->numCU;
-        };
-        if (fits(S)) { if (!c->thinEffort) while (S < hi && fits(S + 1u)) S++; }
-        else {      // the rule above went OVER one item per CU (the power-of-two snap: 9 x (8192 -> 4096) 24 -> 32 slices = 288 items, 62.9 us against 46.1 at 24; the `hi`
-                    // bound: 9 x (4096 -> 1024) at 32 slices 20.6 us, at 24 18.9): the most slices that fit, if any do
-            uint32_t s2 = S;
-            while (s2 > lo && !fits(s2)) s2--;
-            if (fits(s2)) S = s2;
-        }
-    }
-    return S;
-}
-
-// Columns per lane for the whole launch (one kernel variant serves all its calls).  FP16: 2; 1 when a small group would
-// otherwise leave most of the chip without an item (small matrices); 4 for groups of >= 8 calls (fewer, fatter items: less
-// fixed work per byte) unless that leaves the launch with between one and three items per CU -- half the chip would then
-// run two workgroups per CU in lockstep with the other half's one -- or with less than half an item per CU (measured,
-// 4096x11008: 8 calls 7.9 vs 8.4 us/call, 16 calls 7.2 vs 6.6, 32 calls 5.7 vs 6.3).  Q4 (a word = 4 sub-buckets): 1, or 2 from 8 calls on.
-static int pick_elems(const effort_ctx* c, Format fmt, int n, const effort_w* const* ws) {
-    if (c->tuneE) return c->tuneE;
-    if (fmt != kFp16) {      // measured, 4096x11008 Q4: 32 calls 5.3 vs 6.4 us/call, 8 calls 8.3 vs 8.3, 2 calls 20.8 vs 18.8
-        if (n < 8) return 1;
-        if (n < 10) {        // (8 / 9 calls: one E = 1 item per CU where that fits: q4_one_per_cu)
-            uint32_t t1 = 0, inDim = 0, tMax = 0;
-            bool same = true;
-            for (int i = 0; i < n; i++) if (ws[i]) {
-                const uint32_t t = (ws[i]->cols + 63u) / 64u;
-                t1 += t; same = same && (tMax == 0 || t == tMax); tMax = tMax > t ? tMax : t; inDim = inDim > ws[i]->inDim ? inDim : ws[i]->inDim;
-            }
-            if (q4_one_per_cu(c, inDim, tMax, n, same ? 0u : t1)) return 1;
-        }
-        if (n >= 10) {       // (one round of narrow, tall items where that fits: q4_one_round)
-            uint32_t t1 = 0, inDim = 0;
-            for (int i = 0; i < n; i++) if (ws[i]) { t1 += (ws[i]->cols + 63u) / 64u; inDim = inDim > ws[i]->inDim ? inDim : ws[i]->inDim; }
-            if (q4_one_round(c, inDim, t1)) return 1;
-        }
-        return 2;
-    }
-    if (c->tuneS) return 2;
-    auto group_tiles = [&](int E) {
-        uint32_t t = 0;
-        for (int i = 0; i < n; i++) if (ws[i]) t += (ws[i]->cols + 64 * E - 1) / (64 * E);
-        return t;
-    };
-    auto items = [&](int E) {
-        uint32_t t = 0;
-        const uint32_t gt = group_tiles(E);
-        for (int i = 0; i < n; i++) if (ws[i]) t += (ws[i]->cols + 64 * E - 1) / (64 * E) * pick_slices(c, ws[i], n, E, gt, false);
-        return t;
-    };
-    const uint32_t numCU = (uint32_t)c->numCU;
-    // how much of its column tiles' lanes a choice keeps busy: a narrow handle -- a column shard of a multi-GPU split, 11008
-    // outputs over 8 ranks = 86 columns -- fills a third of ONE 256-column tile (E = 4: 22 of 64 lanes), two thirds at E = 2
-    auto fill = [&](int E) {
-        double used = 0, have = 0;
-        for (int i = 0; i < n; i++) if (ws[i]) { used += ws[i]->cols; have += (double)((ws[i]->cols + 64 * E - 1) / (64 * E)) * 64 * E; }
-        return have > 0 ? used / have : 1.0;
-    };
-    const double f1 = fill(1), f2 = fill(2), f4 = fill(4), best = f1 > f2 ? (f1 > f4 ? f1 : f4) : (f2 > f4 ? f2 : f4);
-    if (n >= 8) {
-        const uint32_t i4 = items(4);
-        if (((i4 > numCU / 2 && i4 <= numCU) || i4 >= 3u * numCU) && f4 >= 0.8 * best) return 4;
-        if (f2 >= 0.8 * best) return 2;
-        // 64-column tiles because 128-column ones would leave lanes idle (k sequences' Wq | Wk | Wv: 4096 + 1024 + 1024 outputs fill 3/4 of their 128-column tiles) --
-        // unless the 64-column items outnumber the CUs at the fewest slices and the 128-column ones do not: a launch of one item per CU at 3/4 lane fill beats a
-        // second round (6 / 7 / 8 sequences, 18 / 21 / 24 calls: 37.6 -> 32.7 / 39.3 -> 33.8 / 39.7 -> 34.0 us per launch; 10 sequences overflow either way and stay)
-        if (c->nLanes <= 1 && f2 >= 0.7 * best) {
-            uint32_t p1 = 0, p2 = 0;
-            for (int i = 0; i < n; i++) if (ws[i]) {
-                const uint32_t lo = ((ws[i]->inDim + 511u) / 512u + 7u) / 8u * 8u;
-                p1 += ((ws[i]->cols + 63u) / 64u * lo + 7u) / 8u * 8u; p2 += ((ws[i]->cols + 127u) / 128u * lo + 7u) / 8u * 8u;
-            }
-            if (p1 > numCU && p2 <= numCU) return 2;
-        }
-        return 1;
-    }
-    const uint32_t i2 = items(2);
-    if (f2 < 0.8 * best) return 1;
-    // 3..7 calls of BIG matrices whose E = 2 items overflow one round of CUs even at the fewest slices (6 calls of 4096x11008: 6 x 6 tiles x 8 = 288 items, the 32
-    // over the 256 CUs run as a round of their own) while E = 4 items fit: E = 4, and pick_slices then fills the round (18 tiles x 13 slices = 234 items)
-    if (n >= 3 && f4 >= 0.8 * best && c->nLanes <= 1) {
-        uint32_t lo2 = 0, lo4 = 0;
-        for (int i = 0; i < n; i++) if (ws[i]) {
-            const uint32_t lo = ((ws[i]->inDim + 511u) / 512u + 7u) / 8u * 8u;
-            lo2 += (ws[i]->cols + 127u) / 128u * lo; lo4 += (ws[i]->cols + 255u) / 256u * lo;
-        }
-        if (lo2 > numCU && lo4 <= numCU * 15u / 16u) return 4;
-    }
-    // narrow matrices (<= 256 bucket columns: 4096 outputs) in small groups: 64-column tiles -- more tiles, each reduced by its
-    // own last arriver (measured, us per launch at 25 %: Wq|Wk|Wv 21.2 vs 23.8, 14336 -> 4096 lone 26.6-27.5 vs 29.7)
-    bool narrow = true;
-    for (int i = 0; i < n; i++) narrow = narrow && (!ws[i] || ws[i]->cols <= 256u);
-    // (... for launches that have the chip to themselves, and for lone calls.  GROUPS on a context with lanes -- launches in flight beside one another, the CUs
-    //  never short of items -- want the fatter 128-column tiles: four in flight, us per launch E = 1 / E = 2: 14336 -> 4096 x 2 / 3 / 4 / 6 calls 14.7 / 13.0, 21.6 / 16.9,
-    //  28.6 / 22.3, 44.6 / 31.7; 4096x4096 x 2 / 3 / 4 / 6: 7.7 / 6.7, 10.9 / 7.8, 10.7 / 10.2, 13.1 / 11.8; lone calls 9.7 / 10.0 and 5.4 / 5.9 -- round 6, third session,
-    //  profiles/r06_one_round_groups.txt)
-    if (narrow && f1 >= 0.8 * best && n >= 3 && c->nLanes <= 1 && f2 >= 0.8 * best) {
-        // ... unless the 64-column tiles overflow ONE round of CUs even at the fewest slices while the 128-column tiles fit it (tall narrow matrices: 3 calls of 11008 -> 4096
-        // are 3 x 4 tiles x 24 slices = 288 items, at E = 2 144 -- and pick_slices then fills the round: 35.6 -> 27.9 us per launch, 4 / 5 calls -15 / -7 %, 3 x (14336 -> 4096) -12 %)
-        uint32_t p1 = 0, p2 = 0;
-        for (int i = 0; i < n; i++) if (ws[i]) {
-            const uint32_t lo = ((ws[i]->inDim + 511u) / 512u + 7u) / 8u * 8u;
-            p1 += ((ws[i]->cols + 63u) / 64u * lo + 7u) / 8u * 8u; p2 += ((ws[i]->cols + 127u) / 128u * lo + 7u) / 8u * 8u;
-        }
-        if (p1 > numCU && p2 <= numCU) return 2;
-    }
-    if (narrow && f1 >= 0.8 * best && !(c->nLanes > 1 && n >= 3)) return 1;      // (pairs keep the lone calls' tiles: -11 % left on the table, and a pair's bits do not depend on the lanes)
-    return (i2 * 10u < numCU * 3u / 4u * 6u && items(1) > i2) ? 1 : 2;
-}
-
-static int choose_geom(const effort_ctx* c, const effort_w* w, int groupSize, int E, MulGeom* g, int* Wout, int* Eout, uint32_t sliceMult = 1, uint32_t groupTiles = 0) {
-    const int W = c->tuneW ? c->tuneW : 8;                 // 8 waves per workgroup
-    if (!supported(W, E)) return EFFORT_ERR_ARG;
-    const uint32_t nacc = w->fmt == kFp16 ? 16 : 32;
-    g->inDim = w->inDim; g->outDim = w->outDim; g->cols = w->cols; g->rowsPerIn = w->rowsPerIn;
-    g->expertRows = w->rowsPerIn * w->inDim; g->numExperts = w->numExperts;
-    g->tiles = (w->cols + 64 * E - 1) / (64 * E);
-    g->elems = (uint32_t)E;
-    g->rowPitch = w->rowPitch;
-    const uint32_t tileFloats = nacc * E * 64;
-    const size_t ldsMax = 160 * 1024;
-    uint32_t S;
-    if (c->tuneS) S = c->tuneS;                            // any count: the item grid is padded to a multiple of 8 slices
-    else {
-        const uint32_t want = pick_slices(c, w, groupSize, E, groupTiles) * sliceMult;
-        const uint32_t cap = (c->numCU * 2u) / g->tiles / 8 * 8;              // one round of workgroups
-        S = cap < want ? cap : want;
-    }
-    if (S > w->inDim) S = w->inDim / 8 * 8;
-    if (S < 1) S = 1;
-    const uint32_t maxCand = bucket_mul_max_candidates(W);
-    for (;;) {
-        g->sliceRows = (w->inDim + S - 1) / S;
-        g->slices = (w->inDim + g->sliceRows - 1) / g->sliceRows;
-        g->sliceLog2 = 0; while ((1u << g->sliceLog2) < g->sliceRows) g->sliceLog2++;
-        g->slots = w->fmt == kFp16 ? (g->rowsPerIn << g->sliceLog2) : g->sliceRows * 8u;
-        const size_t lds = bucket_mul_lds_bytes(w->fmt, W, E, *g, true);    // (whether the launch will be a lean plain grid is known only once all its calls are: budget for the larger plan, the lean one's)
-        const bool fits = lds <= ldsMax && g->slots <= maxCand && (size_t)g->slots * 4 + (size_t)g->sliceRows * 8 + 1024 <= 65536 &&   // staged regions below 64 KB
-                          (w->fmt == kFp16 ? (1u << g->sliceLog2) <= 64u * (uint32_t)W : g->sliceRows <= 128u * (uint32_t)W);   // a thread stages one (Q4: two) inputs of the slice
-        const size_t slab = (size_t)g->slices * g->tiles * tileFloats * 4;
-        if (fits && slab <= c->slabBytes) break;
-        if (!fits) { S += 1; if (S > w->inDim + 8) return EFFORT_ERR_SHAPE; }
-        else return EFFORT_ERR_SHAPE;
-    }
-    *Wout = W; *Eout = E;
-    return EFFORT_OK;
-}
-
 static int ensure_timing(effort_ctx* c) {
     if (c->ev) return EFFORT_OK;
     c->ev = new (std::nothrow) hipEvent_t[effort_ctx::kMaxSamples * 4]();       // (value-initialised: effort_destroy walks the whole array)
@@ -854,19 +727,45 @@ static int ensure_timing(effort_ctx* c) {
     return EFFORT_OK;
 }
 
-// One launch for a group of independent calls (a lone call is a group of one).
+// ---- launch planning: the inputs of plan_group (plan.hip) ------------------------------------------
+static PlanEnv plan_env(const effort_ctx* c, bool laned, bool thinEffort) {
+    PlanEnv env;
+    env.numCU = c->numCU; env.nLanes = c->nLanes; env.laned = laned;
+    env.persistent = c->persistent; env.tuneW = c->tuneW; env.tuneE = c->tuneE; env.tuneS = c->tuneS;
+    env.splitCutoff = c->splitCutoff; env.clock = c->clock;
+    env.slabBytes = c->slabBytes; env.maxTiles = effort_ctx::kMaxTiles; env.maxSlices = effort_ctx::kMaxSlices;
+    env.thinEffort = thinEffort;
+    // The A/B switches below read the environment in LAB builds only (-DEFFORT_LAB: tools/build_variant*.sh); the shipped
+    // library has no getenv on this path.
+#ifdef EFFORT_LAB
+    static const uint32_t ablate = getenv("EFFORT_ABLATE") ? (uint32_t)atoi(getenv("EFFORT_ABLATE")) : 0u;   // profiling only
+    static const bool noJobs = getenv("EFFORT_NO_CUTJOBS") != nullptr, noCompact = getenv("EFFORT_NO_COMPACT_MEANS") != nullptr;
+    env.ablate = ablate; env.noJobs = noJobs; env.noCompact = noCompact;
+    if (getenv("EFFORT_TAIL_CALLS")) {       // profiling knobs (read at every call: tools/qbench.py --tails sweeps them in one process)
+        env.tailCalls = atoi(getenv("EFFORT_TAIL_CALLS"));
+        env.tailMult = getenv("EFFORT_TAIL_MULT") ? atoi(getenv("EFFORT_TAIL_MULT")) : 2;
+    }
+#endif
+    return env;
+}
+static PlanCall plan_call(const effort_w* w, int pre, bool resid) {
+    return PlanCall{w->inDim, w->outDim, w->cols, w->rowsPerIn, w->rowPitch, w->numExperts, w->means16 != nullptr, (uint16_t)pre, resid};
+}
+// The launch's mean effort is under 8 %: PlanEnv::thinEffort.
+static bool thin_effort(int n, const double* efforts) {
+    double sum = 0.0;
+    for (int i = 0; i < n; i++) sum += efforts[i];
+    return sum < 0.08 * n;
+}
+
+// One launch for a group of independent calls (a lone call is a group of one): validate, plan, choose the lane, then per launch of the
+// plan copy it and the pointers into the kernel arguments and launch.
 static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws, const float* const* vs,
                     const uint32_t* const* expNos, float* const* outs, const double* efforts,
                     const int* prologues = nullptr, const void* const* vAux = nullptr, const float* const* resids = nullptr) {
     if (!c || !ws || !vs || !outs || !efforts) return fail(c, EFFORT_ERR_ARG, "bucketmul: null argument");
     if (n < 1 || n > kMaxGroup) return fail(c, EFFORT_ERR_ARG, "bucketmul: group size outside 1..32");
-    // The A/B switches below read the environment in LAB builds only (-DEFFORT_LAB: tools/build_variant*.sh); the shipped
-    // library has no getenv on this path.
-#ifdef EFFORT_LAB
-    static const uint32_t ablate = getenv("EFFORT_ABLATE") ? (uint32_t)atoi(getenv("EFFORT_ABLATE")) : 0u;   // profiling only
-#else
-    constexpr uint32_t ablate = 0u;
-#endif
+    PlanCall pc[kMaxGroup];
     for (int i = 0; i < n; i++) {                      // every argument first: nothing is launched for a group with a bad call
         if (!ws[i] || !vs[i] || !outs[i]) return fail(c, EFFORT_ERR_ARG, "bucketmul: null argument");
         if (ws[i]->dead) return fail(c, EFFORT_ERR_ARG, "bucketmul: the handle was freed (its buffers live on only for its column shards)");
@@ -879,293 +778,54 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
         // input does not exist (bucket_mul.hip, phase O).  A residual alone, or a handle without outliers, works at any size.
         if (pre && fmt == kQ4 && ws[i]->olBlockPtr && (uint32_t)ws[i]->inDim > bucket_mul_ol_lds_floats())
             return fail(c, EFFORT_ERR_SHAPE, "bucketmul: an input prologue on a Q4 handle with outliers needs inDim <= 16384 (materialise the input, or register without outliers)");
+        pc[i] = plan_call(ws[i], pre, resids && resids[i]);
     }
-    { double sum = 0.0; for (int i = 0; i < n; i++) sum += efforts[i]; c->thinEffort = sum < 0.08 * n; }
-    const int groupE = pick_elems(c, fmt, n, ws);         // columns per lane: one choice for a group launch
+    LaneChoice lc;
+    lc.laned = c->nLanes > 1 && !c->timing && !c->clock;
+    const PlanEnv env = plan_env(c, lc.laned, thin_effort(n, efforts));
+    GroupPlan plan;
+    if (plan_group(fmt, env, n, pc, &plan) != EFFORT_OK) return fail(c, plan.err, plan.msg);
     const bool tm = c->timing && c->nSamples < effort_ctx::kMaxSamples;
     hipEvent_t* ev = tm ? c->ev + 4 * c->nSamples : nullptr;
-    // ---- which lane (overlap mode): the launch may run beside the launches in flight on the OTHER lanes unless it reads or
-    // writes what one of them writes, or writes what one of them reads; then it waits for that lane (or simply joins it: a
-    // lane's stream is in order).  Always ordered after everything enqueued on the context's stream before this call.
-    // The lane is CHOSEN here and forked (made to wait) only when the first kernel of the group is about to be launched:
-    // a group that fails validation or finds no launch geometry has then touched no stream.  From the fork on, every way out
-    // records the lane's `done` event and marks the lane pending (LaneGuard), so a later join -- in particular the join a
-    // caller owes the capturing stream before it ends a hipGraph capture -- always rejoins a lane that was forked.
-    int li = 0;
-    const bool laned = c->nLanes > 1 && !c->timing && !c->clock;
-    std::vector<Lane::Range> rd, wr;
-    int hazard[effort_ctx::kMaxLanes], nh = 0;
-    unsigned long long capNow = 0;
-    if (laned) {
-        capNow = capture_of(c->stream);
-        if (!lanes_match_capture(c, capNow)) return EFFORT_ERR_ARG;
-        // bounded bookkeeping: a caller may enqueue arbitrarily many multiplies between joins (helpers/gpu.swift:109-119: one
-        // eval() per token); once a lane has recorded kMaxRanges ranges the lanes are JOINED -- the context's stream waits for
-        // all of them, and every later launch forks from that stream -- never forgotten
-        bool full = false;
-        for (int i = 0; i < c->nLanes; i++) full = full || c->lane[i].reads.size() + c->lane[i].writes.size() > effort_ctx::kMaxRanges;
-        if (full) { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
-        auto add = [](std::vector<Lane::Range>& v, const void* p, size_t bytes) { if (p && bytes) v.push_back({(uintptr_t)p, (uintptr_t)p + bytes}); };
-        for (int i = 0; i < n; i++) {
-            add(rd, vs[i], (size_t)ws[i]->inDim * 4);
-            if (expNos && expNos[i]) add(rd, expNos[i], 4);
-            if (vAux && vAux[i]) add(rd, vAux[i], (size_t)ws[i]->inDim * 4);
-            if (resids && resids[i]) add(rd, resids[i], (size_t)ws[i]->outDim * 4);
-            add(wr, outs[i], (size_t)ws[i]->outDim * 4);
-        }
-        for (int i = 0; i < c->nLanes; i++) {
-            const Lane& L = c->lane[i];
-            if (L.pending && (overlaps(rd, L.writes) || overlaps(wr, L.writes) || overlaps(wr, L.reads))) hazard[nh++] = i;
-        }
-        li = nh ? hazard[0] : c->nextLane;
-        // A chain of dependent launches lives on ONE lane and forks from the context's stream only when that stream is busy
-        // (fork_lane).  HIP multiplexes streams over a few hardware queues, and a lane that happens to share its queue with the
-        // context's stream makes hipStreamQuery(context's stream) say "busy" while the LANE works: every link of the chain then
-        // pays the event-record-and-wait fork, +8 us per call (tools/lab/lane_probe.py with EXTRA_CONTEXTS=1: one lane of four;
-        // round 5's bench record showed it at three of five efforts).  Four busy answers in a row on a pure chain: the chain MOVES
-        // to an idle lane -- one cross-lane edge, the ordinary hazard wait below -- where the stream's answer is its own again.
-        // Once between joins: if the busy answers were true (the caller really enqueues between the calls) nothing is lost but that edge.
-        if (nh == 1 && c->busyStreak >= 4 && !c->migrated) {
-            for (int k = 1; k < c->nLanes; k++) {
-                const int cand = (hazard[0] + k) % c->nLanes;
-                if (!c->lane[cand].pending) { li = cand; c->migrated = true; c->busyStreak = 0; break; }
-            }
-        }
-    } else if (c->nLanes > 1) {
-        { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }        // timing modes: one launch at a time, on lane 0
-    }
-    Lane& L = c->lane[li];
-    const hipStream_t st = laned ? L.own : c->stream;
-    struct LaneGuard {                                 // (see above)
-        Lane& L; hipStream_t st; bool forked = false;
-        ~LaneGuard() { if (forked) { L.dirty = true; L.pending = true; } }     // (the event itself: lane_mark, when somebody waits for the lane)
-    } guard{L, st};
-    auto fork_lane = [&]() -> int {                    // before the group's first launch
-        if (!laned || guard.forked) return EFFORT_OK;
-        // "after everything enqueued on the context's stream before this call": an event recorded there, the lane waits -- UNLESS the
-        // stream is idle: then everything enqueued on it has completed and there is nothing to wait for.  That is the state of a
-        // caller who enqueues multiply after multiply and evaluates once (helpers/gpu.swift:109-119; the reference's own timing
-        // loop, benchmarks/benchmark.swift:245-257): all its work sits on the lanes, and the two HIP calls plus the cross-stream
-        // edge per call made that loop 45 % SLOWER with lanes than without (round 4: 32.5 against 22.5 us per call).  A capturing
-        // stream cannot be queried (and "idle" means nothing inside a capture): there the fork is a graph edge, as before.
-        bool wait = true;
-        if (capNow == 0) {
-            const hipError_t q = hipStreamQuery(c->stream);
-            if (q == hipSuccess) wait = false;
-            else {
-                (void)hipGetLastError();                    // ("not ready" must not linger as the thread's last error: the launchers read it after their kernels)
-                if (q != hipErrorNotReady) return fail(c, EFFORT_ERR_HIP, "hipStreamQuery", q);
-            }
-        }
-        if (wait) {
-            HIP_TRY(c, hipEventRecord(c->forkEv, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(L.own, c->forkEv, 0));
-        }
-        c->busyStreak = (wait && nh == 1 && hazard[0] == li) ? c->busyStreak + 1 : 0;     // (a dependent chain's link that had to fork)
-        guard.forked = true;
-        L.capId = capNow;
-        // (a range the lane holds already is not recorded twice: a loop that multiplies into the same vectors over and over --
-        //  the reference's timing loop -- would otherwise grow the lists to their cap, and every call scan thousands of ranges)
-        auto add_new = [](std::vector<Lane::Range>& have, const std::vector<Lane::Range>& more) {
-            for (const auto& x : more) {
-                bool seen = false;
-                for (const auto& y : have) if (y.lo == x.lo && y.hi == x.hi) { seen = true; break; }
-                if (!seen) have.push_back(x);
-            }
-        };
-        // a lane this launch waits for: from here on this lane's order covers everything that lane has enqueued, so its ranges move
-        // here and it is no longer pending (a join need not wait for it, a later launch that touches those ranges follows THIS lane)
-        for (int k = 0; k < nh; k++) if (hazard[k] != li) {
-            Lane& H = c->lane[hazard[k]];
-            HIP_TRY(c, lane_mark(H));
-            HIP_TRY(c, hipStreamWaitEvent(L.own, H.done, 0));
-            add_new(L.reads, H.reads); add_new(L.writes, H.writes);
-            H.reads.clear(); H.writes.clear(); H.pending = false;
-        }
-        if (!nh) c->nextLane = (c->nextLane + 1) % c->nLanes;
-        add_new(L.reads, rd);
-        add_new(L.writes, wr);
-        return EFFORT_OK;
-    };
-    c->lastLane = li;
+    { const int lrc = choose_lane(c, lc, n, ws, vs, expNos, outs, vAux, resids); if (lrc != EFFORT_OK) return lrc; }
+    Lane& L = c->lane[lc.li];
+    const hipStream_t st = lc.laned ? L.own : c->stream;
+    LaneGuard guard{L};
+    c->lastLane = lc.li;
     if (tm) HIP_TRY(c, hipEventRecord(ev[0], st));
-    GroupKArgs ga;
-    int W = 0, E = 0;
-    uint32_t nGeoms = 0, wg = 0, realItems = 0, first = 0;
-    size_t slabOff = 0; uint32_t tileOff = 0, sliceOff = 0;
-    auto begin = [&](uint32_t firstCall) {
+    for (uint32_t l = 0; l < plan.nLaunches; l++) {    // (more than one: a group of more than kMaxGeoms shapes)
+        const LaunchPlan& lp = plan.launch[l];
+        GroupKArgs ga;
         memset(&ga, 0, sizeof(ga));
         ga.groupDone = L.d_counters + effort_ctx::kMaxTiles - 1;
-        ga.slabs = L.d_slabs; ga.counters = L.d_counters; ga.sliceCounts = L.d_sliceCounts; ga.cutoff = L.d_cutoff + firstCall;
+        ga.slabs = L.d_slabs; ga.counters = L.d_counters; ga.sliceCounts = L.d_sliceCounts; ga.cutoff = L.d_cutoff + lp.first;
         ga.tstamp = c->clock ? c->d_tstamp : nullptr;
-        ga.ablate = ablate; ga.split = (c->splitCutoff ? 1u : 0u) | (c->rowReuse ? 8u : 0u); ga.trace = (c->clock && c->trace) ? 1u : 0u;
+        ga.ablate = env.ablate; ga.trace = (c->clock && c->trace) ? 1u : 0u;
+        ga.split = (c->splitCutoff ? 1u : 0u) | (lp.compact ? 4u : 0u) | (c->rowReuse ? 8u : 0u);
         ga.numCU = (uint32_t)c->numCU; ga.queue = L.d_queue;
-        nGeoms = 0; wg = 0; realItems = 0; first = firstCall;
-    };
-    auto flush = [&]() -> int {                        // one kernel launch for the calls gathered so far
-        // grid: persistent workgroups once the items outnumber what the chip holds at R per CU
-        const uint32_t R = c->persistent < 0 ? 2u : (uint32_t)c->persistent;
-        // FP16 on a context WITHOUT lanes -- one launch on the chip at a time -- stays a PLAIN grid: the lean kernel (half the
-        // instructions, every workgroup evaluates its cutoff at once instead of awaiting a job), and the dispatcher hands the third round of workgroups
-        // to whichever CU frees a slot.  Round 6, 4096x11008, us per launch persistent -> plain: 12 calls 80.0 -> 74.9, 16: 89.9 -> 87.4, 20: 111.9 -> 103.2,
-        // 16 at 50 % effort 157.6 -> 145.8, 16 x (4096 -> 14336) 108.9 -> 101.8, 24 / 32 calls level (122.2 / 122.4, 153.0 / 152.2), 32 at 10 % +2 %;
-        // with four launches in flight the persistent grid wins (16 calls 66.9 against 67.6, 32: 127.2 against 130.1): lanes keep it from 2 per CU on
-        // (profiles/r06_plain_vs_persistent.txt).
-        // (1024 items -- 32 calls of 4096 -> 14336 -- 205.4 -> 197.7; 1536 -- 32 calls at E = 2 -- plain 0.98 x the heuristic's launch where persistent was 1.04 x:
-        //  plain up to six items per CU, as far as was measured)
-        const uint32_t perCU = (c->persistent < 0 && fmt == kFp16 && !laned) ? 6u : R;
-        ga.persistent = (R && realItems > ga.numCU * perCU) ? R : 0u;      // (the items that exist, not the padded item range)
-        // persistent launches evaluate every call's cutoff ONCE, in a job of its own at the head of the item queues, instead
-        // of once per workgroup and call (measured: 6.8 of the ~90 us of an item at 32 calls per launch)
-        bool plain = true;
-        for (uint32_t i = 0; i < ga.count; i++) plain = plain && !ga.call[i].pre;
-#ifdef EFFORT_LAB
-        static const bool noJobs = getenv("EFFORT_NO_CUTJOBS") != nullptr;
-#else
-        constexpr bool noJobs = false;
-#endif
-        ga.cutJobs = (ga.persistent && !c->splitCutoff && plain && !noJobs) ? (ga.count + 7u) / 8u * 8u : 0u;
-        // FP16: the multiply stages the compact row means where every slice starts on an even row (an LDS-direct load lands two):
-        // a quarter of the lines of the 8-byte stats entries, half the loads.  Persistent launches, and the plain grids the lean
-        // instantiation serves (8 waves, no stamps): with the path a template parameter it costs them no code (as a run-time
-        // switch inside one kernel it cost lone calls 3 %); measured on plain grids: decode 298 -> 300 tokens/s.
-#ifdef EFFORT_LAB
-        static const bool noCompact = getenv("EFFORT_NO_COMPACT_MEANS") != nullptr;
-#else
-        constexpr bool noCompact = false;
-#endif
-        const bool leanGrid = ga.persistent == 0u && W == 8 && !c->clock && !ablate;      // (launch_mul_t's condition for the lean instantiations)
-        bool compact = fmt == kFp16 && !noCompact && (leanGrid || (ga.persistent != 0u && plain));    // lean: with prologues / residuals too
-        for (uint32_t i = 0; compact && !leanGrid && i < ga.count; i++) compact = !ga.call[i].resid;
-        for (uint32_t i = 0; compact && i < ga.count; i++) {
-            const MulGeom& g = ga.geom[ga.call[i].geom];
-            compact = ws[first + i]->means16 != nullptr && g.inDim % 2u == 0u && g.sliceRows % 2u == 0u;
+        ga.count = lp.count; ga.totalTiles = lp.totalTiles; ga.totalItems = lp.totalItems;
+        ga.persistent = lp.persistent; ga.cutJobs = lp.cutJobs; ga.staggerSleeps = lp.staggerSleeps;
+        for (uint32_t k = 0; k < lp.count; k++) {
+            const int i = (int)(lp.first + k);
+            const effort_w* w = ws[i];
+            const CallPlan& p = plan.call[i];
+            CallDesc& a = ga.call[k];
+            a.buckets = w->buckets; a.stats = lp.compact ? (const void*)w->means16 : w->stats; a.rankBound = w->rankBound; a.probes = w->probes; a.v = vs[i];
+            a.expNo = expNos ? expNos[i] : nullptr; a.out = outs[i];
+            a.ol = OutlierIndex{fmt == kQ4 ? w->olBlockPtr : nullptr, w->olEntry, w->olMeta};
+            a.q = (uint16_t)(int)((double)(kProbes - 1) * (1.0 - efforts[i]));            // bucketMul.swift:39
+            a.bucketsTrim = (uint16_t)w->viewTrim;
+            a.pre = pc[i].pre; a.vAux = a.pre ? vAux[i] : nullptr; a.resid = resids ? resids[i] : nullptr;
+            a.slabOff = p.slabOff; a.tileOff = (uint16_t)p.tileOff; a.sliceOff = (uint16_t)p.sliceOff; a.geom = (uint16_t)p.geom;
+            ga.geom[p.geom] = p.g;
+            ga.wgEnd8[k] = (uint16_t)p.itemEnd8;
+            L.lastSliceOff[i] = p.sliceOff; L.lastSlices[i] = p.g.slices;             // dispatch.size = sum of the per-slice counts
         }
-        if (compact) {
-            for (uint32_t i = 0; i < ga.count; i++) ga.call[i].stats = ws[first + i]->means16;
-            ga.split |= 4u;
-        }
-        // Persistent Q4 launches of a context WITHOUT lanes -- one launch on the chip at a time -- start the second workgroup of every CU ~10 us late,
-        // which takes a CU's pair out of step (bucket_mul_kernel; profiles/r06_ab_q4_stagger.txt: 32 calls per launch 109.5 -> 99.8 us).  With lanes the
-        // launches overlap, the CUs are busy anyway and the wait is a loss (2-5 %): off.  FP16 launches are bound by the CU's pull from memory, not
-        // by an LDS pipe, and their pairs fall out of step by themselves (the older workgroup wins the arbitration two to one): measured, no gain
-        // (profiles/r06_ab_fp16_stagger.txt): off.
-        ga.staggerSleeps = (ga.persistent && fmt == kQ4 && !laned) ? 11u : 0u;
-        const int frc = fork_lane();
-        if (frc != EFFORT_OK) return frc;
-        if (c->splitCutoff && !(ablate & 1u)) HIP_TRY(c, launch_find_cutoff_group(ga, st));
-        HIP_TRY(c, launch_bucket_mul(fmt, W, E, ga, st));
-        return EFFORT_OK;
-    };
-    uint32_t groupTiles = 0;
-    for (int i = 0; i < n; i++) groupTiles += (ws[i]->cols + 64 * groupE - 1) / (64 * groupE);
-    // Thin slices for the LAST TWO calls of an FP16 launch whose last round of workgroups would be nearly empty (round 6, third session;
-    // profiles/r06_tail_slices.txt).  A plain grid's workgroups are handed out in call order, two per CU at a time: 11 calls of 48 items are 528 items --
-    // one round of 512 and 16 stragglers that start when the others END, a whole item's duration for 3 % of the work.  With the last two calls cut into twice the
-    // slices the tail of the launch is made of half-height items: the first of them finish while the round is still running and hand their slots on.  us per
-    // launch, 4096x11008 at 25 %, without / with the rule: 11 calls 72.8 -> 66.0 (-9.4 %), 12: 74.5 -> 69.3 (-7 %), 22: 114.2 -> 108.4 (-5 %), 23: 115.6 -> 110.9
-    // (-4 %), 12 at 10 / 50 / 100 % effort -5.7 / -9.1 / -11.5 %, 11 at 100 % -13.7 %, 19 x (4096 -> 14336) -4.8 %, 11 x (4096 -> 14336) -6 %.  The gain shrinks as
-    // the last round fills -- 13 calls (112 of 512 slots) -2.5 %, 24 calls or 18 x (14336 -> 4096) (128) 0 / +3 % -- so the rule ends at 7/32 of a round.  Applied
-    // to EVERY mid-size launch (its first form) it was level or worse from a quarter-full last round on: 14 / 15 calls +2 / +3 %, 16 at 50 / 100 % effort +2.5 /
-    // +4.5 %, 16 calls of a 4096x4096 matrix (256 items: not even one round) +12 %.  More than
-    // two thin calls, or four times the slices: never better (a thin item pays the same head and hand-off for half the rows); E = 4 launches (32 calls: 149.0 ->
-    // 150.8), persistent grids (151 -> 157) and launches in flight on lanes (a launch's tail runs under the next one's head; round 2: 124.3 -> 125.8): worse, off.
-    // HOW MANY calls: enough that the thin calls' items cover the stragglers (the items past the last whole round), at least two, at most four -- 24 Q4 calls of 24
-    // items are 64 over a round: two thin calls (48 items) 93.7 -> 92.6 us, four (96) 86.3.  Q4 (E = 2 launches past one round of two workgroups per CU are PERSISTENT
-    // grids on a context without lanes: the queue hands the items out in call order just the same): 22 / 24 calls of 4096x11008 93.0 -> 84.9 / 93.7 -> 86.3 us, 17 / 18 x
-    // (4096 -> 14336) 90.0 -> 83.1 / 91.0 -> 83.8, 24 calls at 50 % effort 139.6 -> 128.7; 26 calls (112 over) level.
-    int thinFrom = n;                                     // calls [thinFrom, n) take twice the slices
-    if (groupE == 2 && n >= 8 && !laned && !c->tuneS && c->persistent < 0 && !c->thinEffort) {
-        uint32_t base = 0, it1[kMaxGroup];
-        bool ok = true;
-        for (int i = 0; ok && i < n; i++) {
-            MulGeom g1; int Wi, Ei;
-            memset(&g1, 0, sizeof(g1));
-            ok = choose_geom(c, ws[i], n, groupE, &g1, &Wi, &Ei, 1, groupTiles) == EFFORT_OK;
-            it1[i] = (g1.tiles * g1.slices + 7u) / 8u * 8u;
-            base += it1[i];
-        }
-        const uint32_t round = 2u * (uint32_t)c->numCU, over = ok ? base % round : 0u;
-        // (FP16 stays a plain grid up to six items per CU; Q4 past one round is a persistent grid whatever its size)
-        if (ok && base > round && over != 0u && over * 32u <= round * 7u && (fmt != kFp16 || base <= 6u * (uint32_t)c->numCU)) {
-            int tc = 0;
-            uint32_t thin = 0;
-            while (tc < n && tc < 4 && (tc < 2 || thin < over)) thin += it1[n - 1 - tc++];
-            // the thin geometries: they must exist (more slices than the call has) and fit the launch descriptor's kMaxGeoms shapes beside the others
-            MulGeom seen[kMaxGeoms + 1];
-            uint32_t nSeen = 0, extra = 0;
-            auto note = [&](const MulGeom& g) {
-                uint32_t k = 0;
-                while (k < nSeen && memcmp(&seen[k], &g, sizeof(g)) != 0) k++;
-                if (k == nSeen) { if (nSeen == kMaxGeoms) ok = false; else seen[nSeen++] = g; }
-            };
-            ok = thin >= over;
-            for (int i = 0; ok && i < n; i++) {
-                MulGeom g; int Wi, Ei;
-                memset(&g, 0, sizeof(g));
-                const bool t = i >= n - tc;
-                ok = choose_geom(c, ws[i], n, groupE, &g, &Wi, &Ei, t ? 2u : 1u, groupTiles) == EFFORT_OK;
-                if (ok && t) { const uint32_t it2 = (g.tiles * g.slices + 7u) / 8u * 8u; ok = it2 > it1[i]; extra += it2 - it1[i]; }
-                if (ok) note(g);
-            }
-            if (ok && (fmt != kFp16 || base + extra <= 6u * (uint32_t)c->numCU)) thinFrom = n - tc;
-        }
-    }
-    begin(0);
-    for (int i = 0; i < n; i++) {
-        const effort_w* w = ws[i];
-        MulGeom g;
-        memset(&g, 0, sizeof(g));
-        int Wi, Ei;
-        // the calls at the END of a mid-size group are cut into thinner slices (thinFrom, above): their items are the last ones handed out, and
-        // the launch ends when the last item does
-        uint32_t mult = i >= thinFrom ? 2u : 1u;
-#ifdef EFFORT_LAB
-        if (n >= 8 && !c->tuneS && getenv("EFFORT_TAIL_CALLS")) {       // profiling knobs (read at every call: tools/qbench.py --tails sweeps them in one process): the rule above replaced by "the last tc calls at tailMult x the slices"
-            const int tc = atoi(getenv("EFFORT_TAIL_CALLS"));
-            const int tailMult = getenv("EFFORT_TAIL_MULT") ? atoi(getenv("EFFORT_TAIL_MULT")) : 2;
-            mult = 1;
-            if (i >= n - tc) mult = (uint32_t)tailMult;
-            if (tailMult >= 4 && i >= n - tc && i < n - tc / 2) mult = (uint32_t)tailMult / 2;      // two steps: ... x2 x2 x4 x4
-        }
-#endif
-        int rc = choose_geom(c, w, n, groupE, &g, &Wi, &Ei, mult, groupTiles);
-        if (rc != EFFORT_OK) return fail(c, rc, "bucketmul: no launch geometry for this shape/tuning");
-        if (i == 0) { W = Wi; E = Ei; }
-        else if (Wi != W || Ei != E) return fail(c, EFFORT_ERR_SHAPE, "bucketmul: the calls of a group must agree on the kernel variant");
-        uint32_t gi = 0;
-        while (gi < nGeoms && memcmp(&ga.geom[gi], &g, sizeof(g)) != 0) gi++;
-        if (gi == nGeoms && nGeoms == kMaxGeoms) {     // a launch carries kMaxGeoms distinct shapes: this call opens the next one
-            rc = flush();
-            if (rc != EFFORT_OK) return rc;
-            begin((uint32_t)i);
-            gi = 0;
-        }
-        if (gi == nGeoms) ga.geom[nGeoms++] = g;
-        CallDesc& a = ga.call[(uint32_t)i - first];
-        const size_t slab = (size_t)g.slices * g.tiles * ((fmt == kFp16 ? 16u : 32u) * (uint32_t)Ei * 64u) * 4;
-        if (tileOff + g.tiles + 1 > effort_ctx::kMaxTiles || sliceOff + g.slices > effort_ctx::kMaxSlices || slabOff + slab > c->slabBytes)
-            return fail(c, EFFORT_ERR_SHAPE, "bucketmul: group exceeds the context scratch");
-        a.buckets = w->buckets; a.stats = w->stats; a.rankBound = w->rankBound; a.probes = w->probes; a.v = vs[i];
-        a.expNo = expNos ? expNos[i] : nullptr; a.out = outs[i];
-        a.ol = OutlierIndex{fmt == kQ4 ? w->olBlockPtr : nullptr, w->olEntry, w->olMeta};
-        a.q = (uint16_t)(int)((double)(kProbes - 1) * (1.0 - efforts[i]));            // bucketMul.swift:39
-        a.bucketsTrim = (uint16_t)w->viewTrim;
-        const int pre = prologues ? prologues[i] : 0;
-        a.pre = (uint16_t)pre; a.vAux = pre ? vAux[i] : nullptr; a.resid = resids ? resids[i] : nullptr;
-        a.slabOff = (uint32_t)(slabOff / 256); a.tileOff = (uint16_t)tileOff; a.sliceOff = (uint16_t)sliceOff; a.geom = (uint16_t)gi;
-        wg += (g.tiles * g.slices + 7u) / 8u * 8u;            // the call's item range: a multiple of 8 (item % 8 = the XCD; locate_item)
-        realItems += g.tiles * g.slices;
-        if (wg / 8u > 0xFFFFu) return fail(c, EFFORT_ERR_SHAPE, "bucketmul: group exceeds the launch descriptor's item range");
-        ga.wgEnd8[(uint32_t)i - first] = (uint16_t)(wg / 8u); ga.totalItems = wg;
-        ga.count = (uint32_t)i - first + 1u;
-        ga.totalTiles += g.tiles;
-        L.lastSliceOff[i] = sliceOff; L.lastSlices[i] = g.slices;                   // dispatch.size = sum of the per-slice counts
-        slabOff += (slab + 255) / 256 * 256; tileOff += g.tiles; sliceOff += g.slices;
+        { const int frc = fork_lane(c, lc, guard); if (frc != EFFORT_OK) return frc; }
+        if (c->splitCutoff && !(env.ablate & 1u)) HIP_TRY(c, launch_find_cutoff_group(ga, st));
+        HIP_TRY(c, launch_bucket_mul(fmt, plan.W, plan.E, ga, st));
     }
     L.lastCalls = (uint32_t)n;
-    int rc = flush();
-    if (rc != EFFORT_OK) return rc;
     if (tm) { HIP_TRY(c, hipEventRecord(ev[1], st)); c->nSamples++; }
     return EFFORT_OK;                                  // (LaneGuard records the lane's `done` event)
 }
@@ -1202,9 +862,10 @@ extern "C" int effort_calc_dispatch(effort_ctx* c, const effort_w* w, const floa
     { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
     Lane& L = c->lane[0];
     c->lastLane = 0;
-    MulGeom g; int W, E;
-    int rc = choose_geom(c, w, 1, pick_elems(c, w->fmt, 1, &w), &g, &W, &E);
-    if (rc != EFFORT_OK) return fail(c, rc, "calc_dispatch: geometry");
+    const PlanCall pc = plan_call(w, 0, false);
+    GroupPlan plan;
+    if (plan_group(w->fmt, plan_env(c, false, false), 1, &pc, &plan) != EFFORT_OK) return fail(c, plan.err, "calc_dispatch: geometry");
+    const MulGeom& g = plan.call[0].g;
     const uint32_t q = (uint32_t)(int)((double)(kProbes - 1) * (1.0 - effort));
     HIP_TRY(c, launch_find_cutoff(v, w->probes, expNo, q, L.d_cutoff, L.d_count, nullptr, c->stream));
     HIP_TRY(c, launch_calc_dispatch(w->fmt, w->stats, v, expNo, L.d_cutoff, g, dispatch, count, L.d_count, c->d_blockScratch, c->stream));
@@ -1237,6 +898,39 @@ extern "C" int effort_debug_slice_counts(effort_ctx* c, int idx, uint32_t* host,
     if (n) HIP_TRY(c, hipMemcpyAsync(host, L.d_sliceCounts + L.lastSliceOff[idx], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return (int)n;
+}
+// The planner without a context: no device, no HIP call (include/effort_hip_debug.h).
+extern "C" int effort_debug_plan(int q4, int numCU, int lanes, int n, const int* inDim, const int* outDim, const int* percentLoad,
+                                 const int* prologue, const int* hasResid, const double* effort, int persistent, int tuneW, int tuneE, int tuneS,
+                                 int* we, int* slices, int* tiles, int* sliceRows, int* launchOf,
+                                 int* launchPersistent, int* launchCutJobs, int* launchCompact, int* launchStagger) {
+    if (numCU < 1 || lanes < 1 || lanes > effort_ctx::kMaxLanes || n < 1 || n > kMaxGroup || !inDim || !outDim || !effort || !we || !slices || !tiles ||
+        !sliceRows || !launchOf || !launchPersistent || !launchCutJobs || !launchCompact || !launchStagger) return EFFORT_ERR_ARG;
+    const Format fmt = q4 ? kQ4 : kFp16;
+    effort_ctx c0;                                     // (a context's defaults; never created: no device behind it)
+    c0.numCU = numCU; c0.nLanes = lanes; c0.persistent = persistent; c0.tuneW = tuneW; c0.tuneE = tuneE; c0.tuneS = tuneS;
+    c0.slabBytes = effort_ctx::kSlabBytes;
+    PlanCall pc[kMaxGroup];
+    for (int i = 0; i < n; i++) {
+        const int load = q4 ? 8 : (percentLoad ? percentLoad[i] : 16);
+        if (inDim[i] <= 0 || outDim[i] <= 0 || check_shape((uint32_t)inDim[i], (uint32_t)outDim[i]) != EFFORT_OK || load < 1 || load > 16) return EFFORT_ERR_SHAPE;
+        if (!(effort[i] >= 0.0 && effort[i] <= 1.0)) return EFFORT_ERR_EFFORT;
+        const uint32_t cols = (uint32_t)outDim[i] / (q4 ? 32u : 16u);
+        pc[i] = PlanCall{(uint32_t)inDim[i], (uint32_t)outDim[i], cols, (uint32_t)load, cols * 2u, 1u, !q4, (uint16_t)(prologue ? prologue[i] : 0), hasResid && hasResid[i]};
+    }
+    GroupPlan plan;
+    const int rc = plan_group(fmt, plan_env(&c0, lanes > 1, thin_effort(n, effort)), n, pc, &plan);
+    if (rc != EFFORT_OK) return rc;
+    we[0] = plan.W; we[1] = plan.E;
+    for (int i = 0; i < n; i++) {
+        const CallPlan& p = plan.call[i];
+        slices[i] = (int)p.g.slices; tiles[i] = (int)p.g.tiles; sliceRows[i] = (int)p.g.sliceRows; launchOf[i] = (int)p.launch;
+    }
+    for (uint32_t l = 0; l < plan.nLaunches; l++) {
+        const LaunchPlan& lp = plan.launch[l];
+        launchPersistent[l] = (int)lp.persistent; launchCutJobs[l] = (int)lp.cutJobs; launchCompact[l] = lp.compact ? 1 : 0; launchStagger[l] = (int)lp.staggerSleeps;
+    }
+    return (int)plan.nLaunches;
 }
 extern "C" int effort_group_cutoff(effort_ctx* c, int idx, float* host_out) {
     if (!c || !host_out || idx < 0 || (uint32_t)idx >= c->lane[c->lastLane].lastCalls) return EFFORT_ERR_ARG;

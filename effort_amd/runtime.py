@@ -198,6 +198,26 @@ class Gpu:
             pass
 
 
+def plan(calls, *, q4: bool = False, numCU: int = 256, lanes: int = 1, persistent: int = -1, waves: int = 0, elems: int = 0, slices: int = 0) -> dict:
+    """The launch plan of one group (effort_debug_plan: csrc/plan.hip without a context or a device; test / tools hook).
+    ``calls``: (inDim, outDim, effort[, percentLoad[, prologue[, hasResid]]]) per call.  Returns W, E, the per-call lists ``slices``,
+    ``tiles``, ``sliceRows``, ``launch`` and per launch ``persistent``, ``cutJobs``, ``compact``, ``stagger``; raises EffortError
+    where the multiply call would."""
+    n = len(calls)
+    rows = [tuple(c) + (16, 0, 0)[len(c) - 3:] for c in calls]
+    ints = lambda k: (C.c_int * n)(*[int(r[k]) for r in rows])
+    out = [(C.c_int * max(n, 2))() for _ in range(9)]
+    k = _lib.lib().effort_debug_plan(int(q4), numCU, lanes, n, ints(0), ints(1), ints(3), ints(4), ints(5), (C.c_double * n)(*[float(r[2]) for r in rows]),
+                                     persistent, waves, elems, slices, *out)
+    if k < 0:
+        raise _lib.EffortError(k, "plan")
+    we, per_call, per_launch = out[0], out[1:5], out[5:]
+    res = {"W": we[0], "E": we[1]}
+    res.update({name: list(a[:n]) for name, a in zip(("slices", "tiles", "sliceRows", "launch"), per_call)})
+    res.update({name: list(a[:k]) for name, a in zip(("persistent", "cutJobs", "compact", "stagger"), per_launch)})
+    return res
+
+
 _gpus: dict[int, Gpu] = {}
 
 

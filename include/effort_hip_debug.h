@@ -50,6 +50,17 @@ EFFORT_API int effort_debug_stamps(effort_ctx* ctx, unsigned long long* host32);
 /* Kept rows per row slice of call idx of the most recent (group) launch (their sum is dispatch.size); returns the
  * number of slices copied (<= maxSlices), or a negative error code. */
 EFFORT_API int effort_debug_slice_counts(effort_ctx* ctx, int idx, uint32_t* host, int maxSlices);
+/* The launch planner on its own (csrc/plan.hip: plan_group), for the n calls of one group on a device of numCU compute units and a context of
+ * `lanes` lanes: no context, no device, no HIP call -- it runs on a machine without a GPU.  Per call: inDim, outDim, percentLoad (FP16; NULL = 16,
+ * ignored for q4), prologue (EFFORT_PRE_*; NULL = none), hasResid (NULL = none), effort (the launch is "thin" when their mean is under 8 %, as in
+ * the multiply calls).  persistent / tuneW / tuneE / tuneS: effort_set_persistent / effort_set_tuning (-1, 0, 0, 0 = the heuristics).
+ * Fills we[2] = {waves per workgroup, columns per lane}; per call [n]: slices, tiles, sliceRows, launchOf (the launch the call went to: a group
+ * splits when it holds more than four shapes); per launch [n]: persistent workgroups per CU (0: plain grid), cutoff jobs, compact-means bit,
+ * stagger sleeps.  Returns the number of launches, or the negative error code the multiply call would return. */
+EFFORT_API int effort_debug_plan(int q4, int numCU, int lanes, int n, const int* inDim, const int* outDim, const int* percentLoad,
+                      const int* prologue, const int* hasResid, const double* effort, int persistent, int tuneW, int tuneE, int tuneS,
+                      int* we, int* slices, int* tiles, int* sliceRows, int* launchOf,
+                      int* launchPersistent, int* launchCutJobs, int* launchCompact, int* launchStagger);
 /* enable = 3 (device clock + trace): every work item of the most recent multiply launch leaves a 64-byte record
  * {item | workgroup << 32 (bit 63: cutoff job), XCC_ID | HW_ID << 32, six device wall-clock stamps: start, staged,
  * cutoff, selected, streamed, handed over}; copies the first maxRecords (<= 4096) records to host (8 u64 each), followed

@@ -1082,7 +1082,7 @@ def test_aligned_row_pitch_is_bit_identical(ea, oracle_cpu, q4_11008):
     ea.bucketMulGroup([(vd, padded if i & 1 else plain, None, outs[i], 0.25) for i in range(12)])
     g.eval()
     want, n, cutoff = oracle_cpu.bucket_mul(v, b, s, p, inDim, outDim, 0.25)
-    for i in range(12):                              # (the last two calls of this launch are cut into thinner slices, api.hip thinFrom: their own rounding grid)
+    for i in range(12):                              # (the last two calls of this launch are cut into thinner slices, plan.hip thinFrom: their own rounding grid)
         assert g.last_dispatch_count(i) == n and torch.equal(outs[i], outs[0 if i < 10 else 10]) and close(outs[i].cpu().numpy(), want), i
     o2 = torch.zeros(outDim, device=DEV)
     ea.bucketMul(vd, padded, None, o2, 0.25)
@@ -1292,7 +1292,7 @@ def test_timing_hooks_of_the_shipped_library(ea, oracle_cpu):
 def test_slice_counts_that_are_not_multiples_of_eight(ea, oracle_cpu, q4_11008):
     """Slices are dealt to the XCDs in rounds of 8, so a count like 5 or 12 pads the item grid, and the FIRST block of a call can be padding
     (it is for a call whose rotation puts slices >= the count there).  Round 6's Q4 rule launches 10..16 calls as one round of 5-8 tall slices
-    (api.hip q4_one_round), so such counts are the default path now: every call's dispatch.size, BucketMul.cutoff (the hook is written by the
+    (plan.hip q4_one_round), so such counts are the default path now: every call's dispatch.size, BucketMul.cutoff (the hook is written by the
     item of tile 0 / slice 0, which used to be taken for the first block) and product against the oracle -- Q4 groups of 10, 13 and 16 on the
     default geometry, then forced slice counts, lone and grouped, FP16 too."""
     W, L, inDim, outDim = q4_11008
@@ -1332,7 +1332,7 @@ def test_slice_counts_that_are_not_multiples_of_eight(ea, oracle_cpu, q4_11008):
 def test_geometry_rules_of_round_six(ea, oracle_cpu, q4_11008):
     """The launch-geometry rules round 6 added, pinned through the slice-count hook (effort_debug_slice_counts): a lone 4096 -> 14336 call --
     the reference's timed shape -- takes 32 slices (24 = 171 rows in blocks of 256 slots before: pick_slices' power-of-two rule); a 16-call
-    Q4 group on a context WITHOUT lanes launches as one round of 5 tall slices per call, on a context WITH lanes as 8 (api.hip q4_one_round);
+    Q4 group on a context WITHOUT lanes launches as one round of 5 tall slices per call, on a context WITH lanes as 8 (plan.hip q4_one_round);
     a pair of Q4 calls 16 slices; an FP16 launch without lanes whose last round of workgroups would be nearly empty cuts its last two calls into twice
     the slices.  Every product against the oracle."""
     W, L, inDim, outDim = q4_11008
@@ -1364,7 +1364,7 @@ def test_geometry_rules_of_round_six(ea, oracle_cpu, q4_11008):
         wantf, cntf, cutf = oracle_cpu.bucket_mul(v, b, s, p, iD, oD, 0.25)
         assert g.last_dispatch_count() == cntf and g.last_cutoff() == cutf and close(out.cpu().numpy(), wantf)
         # FP16, third session: a launch that has the chip to itself and whose last round of workgroups would be nearly empty (at most 7/32 full: 11 / 12 / 13 / 23 calls of
-        # 48 items are 16 / 64 / 112 / 80 items over a multiple of 512; 14 and 24 calls, 160 and 128, are not) cuts its LAST TWO calls into twice the slices (api.hip do_group: thinFrom); not with lanes
+        # 48 items are 16 / 64 / 112 / 80 items over a multiple of 512; 14 and 24 calls, 160 and 128, are not) cuts its LAST TWO calls into twice the slices (plan.hip plan_group: thinFrom); not with lanes
         oD, iD = 11008, 4096
         Wf, b, s, p = converted(oracle_cpu, oD, iD)
         ewf = gpu_weights(ea, Wf, b, s, p)
@@ -1381,7 +1381,7 @@ def test_geometry_rules_of_round_six(ea, oracle_cpu, q4_11008):
             for i in (0, 1, n - 3, n - 2, n - 1):
                 wantf, cntf, cutf = wants[i % 3]
                 assert g.last_dispatch_count(i) == cntf and g.last_cutoff(i) == cutf and close(outs[i].cpu().numpy(), wantf), (lanes, n, i)
-        # FP16, third session: a group of >= 8 calls on a SMALL matrix takes enough slices to give every CU an item (api.hip pick_slices: fill) --
+        # FP16, third session: a group of >= 8 calls on a SMALL matrix takes enough slices to give every CU an item (plan.hip pick_slices: fill) --
         # 8 calls on 4096 x 4096: 16 slices (8 x 2 tiles x 16 = 256 items; 8 slices left half the CUs idle); and a group of >= 3 calls that fits one round of CUs
         # takes as many slices as keep it at one item per CU, counted as the items are dealt to the XCDs (a call's range padded to a multiple of 8): 9 calls 12
         # slices (9 x 24 = 216), 11 calls 8 (12 slices would be 264)
@@ -1411,6 +1411,45 @@ def test_geometry_rules_of_round_six(ea, oracle_cpu, q4_11008):
             for i in range(n):
                 wantf, cntf, cutf = wants[i % 3]
                 assert g.last_dispatch_count(i) == cntf and g.last_cutoff(i) == cutf and close(outs[i].cpu().numpy(), wantf), (n, i)
+    finally:
+        g.set_overlap(1)
+        g.close()
+
+
+@pytest.mark.parametrize("q4", [False, True])
+def test_reported_plan_is_the_launch(ea, oracle_cpu, q4):
+    """effort_debug_plan -- the planner (csrc/plan.hip) without a context, what tests/test_plan_cpu.py pins on a machine without a GPU -- reports
+    the launch that happens: for groups of 1 / 3 / 9 / 12 calls of the smallest registrable shape (4096 -> 1024, FP16 and Q4) on 1 and 4 lanes, the
+    plan's slices per call for this device's CU count equal what every call of the launch left behind, and the products match the oracle."""
+    from effort_amd import runtime
+    inDim, outDim, efforts = 4096, 1024, (0.25, 0.5, 0.1)
+    vs = [make_v(inDim, seed=700 + i, heavy=bool(i & 1)) for i in range(3)]
+    if q4:                                        # a synthetic bundle: any nibble pattern is a valid bucket word (test_q4_outlier_tables)
+        rng = np.random.default_rng(inDim + outDim)
+        buckets = rng.integers(0, 65536, size=(inDim * 8, outDim // 32), dtype=np.uint16)
+        mean = np.abs(rng.normal(0, 0.02, size=inDim * 8)).astype(np.float32)
+        stats, probes = np.stack([mean, mean], axis=1), rng.normal(0, 0.02, size=4096).astype(np.float16)
+        ew = ea.ExpertWeights(dev16(buckets), devf(stats), dev16(probes), inSize=inDim, outSize=outDim, q4=True)
+        wants = [oracle_cpu.bucket_mul_q4(vs[i], buckets, stats, probes, None, inDim, outDim, e) for i, e in enumerate(efforts)]
+    else:
+        W, b, s, p = converted(oracle_cpu, outDim, inDim)
+        ew = gpu_weights(ea, W, b, s, p)
+        wants = [oracle_cpu.bucket_mul(vs[i], b, s, p, inDim, outDim, e) for i, e in enumerate(efforts)]
+    numCU = torch.cuda.get_device_properties(0).multi_processor_count
+    vd = [devf(v) for v in vs]
+    g = ea.Gpu(0)
+    try:
+        for lanes in (1, 4):
+            g.set_overlap(lanes)
+            for n in (1, 3, 9, 12):
+                plan = runtime.plan([(inDim, outDim, efforts[i % 3], 16) for i in range(n)], q4=q4, numCU=numCU, lanes=lanes)
+                outs = [torch.full((outDim,), float("nan"), device=DEV) for _ in range(n)]
+                ea.bucketMulGroup([(vd[i % 3], ew, None, outs[i], efforts[i % 3]) for i in range(n)], gpu=g)
+                g.eval()
+                assert [len(g.slice_counts(i)) for i in range(n)] == plan["slices"], (lanes, n, plan)
+                for i in range(n):
+                    want, cnt, cutoff = wants[i % 3]
+                    assert g.last_dispatch_count(i) == cnt and g.last_cutoff(i) == cutoff and close(outs[i].cpu().numpy(), want), (lanes, n, i)
     finally:
         g.set_overlap(1)
         g.close()

@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("bucketMul", "bucketMulQ4", "bucketMulGroup", "expertMul", "basicMul", "basicMulExpert", "BucketMul", "BucketMulQ4", "cosineSimilarityTo"):
         from . import bucket_mul as _b
         return getattr(_b, name)
+    if name in ("Sampling", "philox_u", "sample_reference"):
+        from . import sampling as _sm
+        return getattr(_sm, name)
     if name == "bucketize":
         from . import convert as _c
         return _c.bucketize

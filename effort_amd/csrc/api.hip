@@ -16,6 +16,7 @@
 #include "../../include/effort_hip_debug.h"
 #include "effort_internal.h"
 #include "plan.h"
+#include "sample_device.h"
 
 using namespace effort;
 
@@ -1123,6 +1124,22 @@ extern "C" int effort_argmax(effort_ctx* c, const float* logits, int n, uint32_t
     HIP_TRY(c, launch_argmax(logits, (uint32_t)n, idOut, pos, history, (uint32_t)(history ? historyLen : 0), c->d_status + 1, c->stream));
     return EFFORT_OK;
 }
+// The sampled pick (sample.hip).  The settings are read on the device: a captured step serves every seed, temperature, top-k and top-p.
+extern "C" int effort_sample(effort_ctx* c, const float* logits, int n, const effort_sample_params* params, uint32_t* idOut, uint32_t* pos,
+                             uint32_t* history, int historyLen, uint32_t* topkIdx, float* topkVal) {
+    if (!c || !logits || !params || !idOut || !pos || n <= 0 || (history && historyLen <= 0)) return fail(c, EFFORT_ERR_ARG, "sample: bad argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_sample(logits, (uint32_t)n, params, idOut, pos, history, (uint32_t)(history ? historyLen : 0), c->d_status + 1, topkIdx, topkVal,
+                             c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_topk(effort_ctx* c, const float* logits, int n, int k, uint32_t* idx, float* val) {
+    if (!c || !logits || !idx || !val || n <= 0 || k < 1 || k > EFFORT_SAMPLE_MAX_K) return fail(c, EFFORT_ERR_ARG, "topk: bad argument (1 <= k <= 64)");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_topk(logits, (uint32_t)n, (uint32_t)k, idx, val, c->stream));
+    return EFFORT_OK;
+}
+extern "C" uint32_t effort_sample_bits(uint32_t seedLo, uint32_t seedHi, uint32_t stream, uint32_t pos) { return philox_x0(seedLo, seedHi, stream, pos); }
 // Device-side conditions the decode glue could not report through a return code (the position lives in device memory):
 // bit 0 = a step ran past the key/value cache or the history buffer (nothing was written there), bit 1 = argmax over NaN
 // logits (token 0 returned).  Reads and clears the word.

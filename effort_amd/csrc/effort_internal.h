@@ -256,6 +256,11 @@ hipError_t launch_moe_route(const float* h, const uint16_t* w, const uint16_t* g
 hipError_t launch_argmax(const float* logits, uint32_t n, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
                          int* status, hipStream_t st);
 
+// the sampled pick (sample.hip)
+hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
+                         int* status, uint32_t* topkIdx, float* topkVal, hipStream_t st);
+hipError_t launch_topk(const float* logits, uint32_t n, uint32_t k, uint32_t* idx, float* val, hipStream_t st);
+
 hipError_t launch_f32_to_f16(const float* in, uint16_t* out, uint32_t n, hipStream_t st);
 hipError_t launch_cosine(const float* a, const float* b, uint32_t n, float* out3, hipStream_t st);
 hipError_t launch_validate_outliers(const float* outliers, uint64_t n, uint32_t inDim, uint32_t outDim, int* bad, hipStream_t st);

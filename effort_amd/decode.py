@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from .bucket_mul import basicMul, basicMulExpert, bucketMul, bucketMulGroup, bucketMulQ4
 from .runtime import gpu as _gpu
+from .sampling import Sampling
 from .weights import ExpertWeights
 
 
@@ -248,13 +249,20 @@ class Decoder:
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.tokId = torch.zeros(1, dtype=torch.int32, device=dev)
         self.history = torch.zeros(self.maxTokens, dtype=torch.int32, device=dev)
+        self.sample_params = Sampling().to_device(device=dev)     # effort_sample_params, 32 bytes: the sampled pick reads its settings HERE
         self._graphs: dict = {}
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
-    def token_step(self, effort: float = 0.25, dense: bool = False):
+    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None):
+        """``sampling``: None -- the step ends in the greedy pick (effort_argmax); a ``Sampling`` -- its settings are written to
+        ``self.sample_params`` and the step ends in effort_sample; True -- effort_sample on what ``self.sample_params`` holds (how the
+        step is captured: the graph reads the settings from that tensor at every replay)."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         g._bind_stream()
+        sampled = sampling is not None and sampling is not False
+        if isinstance(sampling, Sampling):
+            self.set_sampling(sampling)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
 
         def muls(v, pairs):
@@ -269,7 +277,7 @@ class Decoder:
         ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
         delta = None
         if self.mixed and not dense:
-            return self._token_step_bundles(effort)
+            return self._token_step_bundles(effort, sampled)
         if self.sharded and not dense:
             G = self.groups
             for n, L in enumerate(m.layers):
@@ -283,7 +291,7 @@ class Decoder:
                 G.mul(self.x1, [(L.w2, self.h, {"gate": self.x3, "resid": self.h})], effort)                             # :181-183, in place on h
             ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
             basicMul(self.outNormed, m.output, self.logits)                                           # :222 (replicated: every rank picks the same token)
-            ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+            self._pick(sampled)
             return
         if self.fused_glue and self.moe and not dense:
             # Mixtral, everything folded: 7 launches per layer.  The routing reads h and ffnNorm itself, the experts' w1|w3 take the
@@ -306,7 +314,7 @@ class Decoder:
                 ck(lib.effort_mix2_add(g.ctx, _p(self.h), _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), cfg.stateDim), "mix2_add")   # :190-199
             ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
             basicMul(self.outNormed, m.output, self.logits)                                           # :222
-            ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+            self._pick(sampled)
             return
         if self.fused_glue and not dense:
             fn, fg, fr = "norm" in self.fuse, "gate" in self.fuse, "resid" in self.fuse
@@ -350,7 +358,7 @@ class Decoder:
                     delta = self.ffnOut
             ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
             basicMul(self.outNormed, m.output, self.logits)                                           # :222
-            ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+            self._pick(sampled)
             return
         for n, L in enumerate(m.layers):
             ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(L.attnNorm), _p(self.h_norm), cfg.stateDim), "rmsnorm")
@@ -389,9 +397,44 @@ class Decoder:
                 delta = self.ffnMix
         ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
         basicMul(self.outNormed, m.output, self.logits)                                               # :222
-        ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+        self._pick(sampled)
 
-    def _token_step_bundles(self, effort: float):
+    def _pick(self, sampled: bool):
+        """The closing call of every token step: the next token from ``self.logits``, written to tokId and history[pos]; pos += 1."""
+        g, lib, n, hl = self.g, _lib.lib(), self.cfg.vocab, int(self.history.numel())
+        if not sampled:
+            g.check(lib.effort_argmax(g.ctx, _p(self.logits), n, _p(self.tokId), _p(self.pos), _p(self.history), hl), "argmax")
+        else:
+            g.check(lib.effort_sample(g.ctx, _p(self.logits), n, _p(self.sample_params), _p(self.tokId), _p(self.pos), _p(self.history), hl,
+                                      None, None), "sample")
+
+    def set_sampling(self, sampling: "Sampling"):
+        """Rewrite the device-resident settings of the sampled pick (no graph is touched: the captured step reads this tensor)."""
+        self.g._bind_stream()
+        sampling.to_device(self.sample_params)
+
+    def topk(self, k: int = 16):
+        """mpsTopK of the current logits (effort_topk): (ids, values) of the k largest, value descending, lowest index first among
+        equal values; ids past the number of non-NaN logits are -1 (values -inf).  ids: list of int, values: f32 tensor on the host."""
+        g = self.g
+        g._bind_stream()
+        idx = torch.empty(int(k), dtype=torch.int32, device=self.logits.device)
+        val = torch.empty(int(k), dtype=torch.float32, device=self.logits.device)
+        g.check(_lib.lib().effort_topk(g.ctx, _p(self.logits), self.cfg.vocab, int(k), _p(idx), _p(val)), "topk")
+        g.eval()
+        return idx.cpu().tolist(), val.cpu()
+
+    def pick_among(self, limit_ids) -> int:
+        """The reference's quiz rule (runNetwork.swift:237-249): the 1-based position in ``limit_ids`` of the first of the top 16
+        logits that occurs there, else 99."""
+        limit = [int(x) for x in limit_ids]
+        for i in self.topk(16)[0]:
+            for j, want in enumerate(limit):
+                if want == i:
+                    return j + 1
+        return 99
+
+    def _token_step_bundles(self, effort: float, sampled: bool = False):
         """The token step of a model whose bundles are not all FP16, dispatched per bundle as expertMul does (expertMul.swift:24-38):
         a Q4 bundle with buckets -> the Q4 multiply, a core-only bundle -> dense basicMul, an FP16 bundle -> bucketMul.  Bundles of
         one kind that share an input share ONE group launch (w1|w3).  Glue folds into a launch where the BUNDLES allow it: the norm
@@ -453,7 +496,7 @@ class Decoder:
                 delta = self.ffnOut
         ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
         basicMul(self.outNormed, m.output, self.logits)                                               # :222
-        ck(lib.effort_argmax(g.ctx, _p(self.logits), cfg.vocab, _p(self.tokId), _p(self.pos), _p(self.history), int(self.history.numel())), "argmax")
+        self._pick(sampled)
 
     def _dense_experts(self, L, e0, e1):
         """Dense baseline of the routed FFN: basicMul on the picked expert of each stack of cores, the expert number read on the device
@@ -479,15 +522,18 @@ class Decoder:
             g.check(lib.effort_silu_mul(g.ctx, _p(x1), _p(x3), _p(x2), cfg.hiddenDim), "silu")
             mul(x2, L.w2.core, e, out)
 
-    def _graph(self, effort: float, dense: bool):
+    def _graph(self, effort: float, dense: bool, sampled: bool = False):
         key = ("dense",) if dense else (float(effort),)
+        if sampled:                                              # the ONLY thing sampling adds to the key: its settings are device values
+            key += ("sampled",)
+        pick = True if sampled else None
         if key not in self._graphs:
             self.reset()
-            self.token_step(effort, dense)                       # warm (handles, kernel attributes, rocBLAS)
+            self.token_step(effort, dense, pick)                 # warm (handles, kernel attributes, rocBLAS)
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                self.token_step(effort, dense)
+                self.token_step(effort, dense, pick)
             self.g._bind_stream()
             self._graphs[key] = gr
         return self._graphs[key]
@@ -506,14 +552,18 @@ class Decoder:
         self.history.zero_()
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
-            collect_logits: bool = False):
+            collect_logits: bool = False, sampling=None):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
+        ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
+        (position, stream) under the seed) instead of the greedy one; the step graph is shared by all settings.
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
-        gr = self._graph(effort, dense)
+        gr = self._graph(effort, dense, sampling is not None)
         self.reset()
+        if sampling is not None:
+            self.set_sampling(sampling)
         logits = []
         t0, timed = None, 0
         for step in range(numTokens):

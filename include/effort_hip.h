@@ -331,6 +331,43 @@ EFFORT_API int effort_argmax(effort_ctx* ctx, const float* logits_dev, int n, ui
  * bit 0 of the context's decode status; an argmax over NaN logits returns token 0 and raises bit 1.  Reads and clears it. */
 EFFORT_API int effort_decode_status(effort_ctx* ctx, int* host_out);
 
+/* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */
+
+/* The settings of effort_sample live in DEVICE memory (a token step is captured once into a hipGraph and graphs are kept for the
+ * life of the process: a value in the kernel arguments would need a graph per seed or temperature).  32 bytes, little endian, no
+ * padding.  The host cannot validate device values, so the kernel sanitises them: top_k is clamped to [1, min(64, n)];
+ * temperature <= 0 or not finite means the pick is the largest logit (greedy); top_p outside (0, 1] is treated as 1. */
+#define EFFORT_SAMPLE_MAX_K 64
+typedef struct effort_sample_params {
+    float temperature;
+    float top_p;
+    uint32_t top_k;
+    uint32_t seed_lo;             /* Philox key = (seed_lo, seed_hi) */
+    uint32_t seed_hi;
+    uint32_t stream;              /* counter word 1: independent sequences under one seed */
+    uint32_t reserved[2];
+} effort_sample_params;
+
+/* Takes effort_argmax's place in a sampled token step (one launch of one workgroup).
+ *  1. The K = top_k largest logits, sorted by value descending, lowest index first among equal values (-0.0 == +0.0; NaN is never
+ *     selected; -inf is an ordinary value) -- the reference's mpsTopK (helpers/mps.swift:49-80).  If topk_idx_dev / topk_val_dev are given
+ *     (either may be NULL) they receive the K indices and values (the logits as stored); entries past the number of non-NaN
+ *     logits get 0xFFFFFFFF / -inf.
+ *  2. One lane, f32, in rank order: w_j = expf((v_j - v_0) / temperature), running sums c_j; the nucleus is the shortest prefix with
+ *     c_j >= top_p * c_{K-1}, its mass S; the pick is the smallest j of the nucleus with c_j > u * S, or its last entry if rounding leaves
+ *     none.  An infinite v_0 picks rank 0.
+ *  3. u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 at counter (*pos_dev, stream, 0, 0) under key (seed_lo, seed_hi)
+ *     (effort_sample_bits): a replayed graph draws anew at every position, a run is reproducible from its seed.
+ *  4. What effort_argmax writes: *id_out_dev, history_dev[*pos_dev] (or decode status bit 0 past historyLen), *pos_dev += 1; every logit
+ *     NaN: token 0 and status bit 1.  With top_k = 1 or a greedy temperature the result is effort_argmax's, bit for bit. */
+EFFORT_API int effort_sample(effort_ctx* ctx, const float* logits_dev, int n, const effort_sample_params* params_dev, uint32_t* id_out_dev,
+                  uint32_t* pos_dev, uint32_t* history_dev, int historyLen, uint32_t* topk_idx_dev, float* topk_val_dev);
+/* mpsTopK(v:topK:) (helpers/mps.swift:49-80): step 1 of effort_sample alone, 1 <= k <= 64 (the reference asks for 16).  idx_dev / val_dev
+ * receive k entries; those past the number of non-NaN logits (n < k, or NaN logits) are 0xFFFFFFFF / -inf.  No position, no status. */
+EFFORT_API int effort_topk(effort_ctx* ctx, const float* logits_dev, int n, int k, uint32_t* idx_dev, float* val_dev);
+/* Host only -- no context, no HIP call: x0 of the draw at (seed, stream, pos), from the same definition the kernel compiles. */
+EFFORT_API uint32_t effort_sample_bits(uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, uint32_t pos);
+
 /* ---- weight layout converter ------------------------------------------------------------------- */
 
 /* func bucketize(_:outTensorsPref:tensors:goQ8:false) -- convert.swift:209-260 with kernels getProbes,

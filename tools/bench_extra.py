@@ -4,7 +4,9 @@
 (heavy-tailed input, a structured matrix, the structured decode model), the other shapes, `shard_projection` (BASELINE config 4's
 column split projected on one GPU), the one-GPU `layer_latency` (a world of one through RCCL + projected ranks), `decode_q4` (the
 decode loop on the reference's Q4 model beside the FP16 one) and `decode_mixtral` (the routed decode loop at Mixtral-8x7B shapes: dense,
-and effort with the glue kernels separate or folded; its record also goes to profiles/r07_decode_mixtral.json).
+and effort with the glue kernels separate or folded; its record also goes to profiles/r07_decode_mixtral.json) and `decode_sampled` (the
+decode loop ending in the device-side top-k / top-p / temperature pick beside the greedy one, and the two closing kernels alone; its
+record also goes to profiles/r08_decode_sampled.json).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -21,7 +23,7 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral")
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled")
 
 
 def by_streams(b, res):
@@ -309,6 +311,94 @@ def decode_mixtral(b, res):
     del plain, folded, model
 
 
+def decode_sampled(b, res):
+    """Sampled decode beside greedy decode in ONE process (the yardstick is this process's own greedy figure): Mistral-7B shapes, 25 %
+    effort, 64 tokens -- greedy, sampled (top_k 40, temperature 0.8), sampled (top_k 64, top_p 0.9), greedy again -- and the closing
+    kernels alone: argmax_kernel and sample_kernel at n = 32000, device events around replays of a captured graph of that ONE launch
+    (and of 64 launches in a row: the graph-launch overhead spread over 64)."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    from effort_amd.sampling import Sampling
+    torch = b.torch
+    b.g.set_tuning(0, 0, 0)
+    torch.cuda.empty_cache()
+    prompt, nt = [1, 733, 16289, 28793, 22557], 64
+    model = Model.random(MistralConfig(), seed=1)
+    dec = Decoder(model, maxTokens=nt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+
+    def tps(**kw):
+        best, ids = 0.0, None
+        for _ in range(3):
+            ids, dt, _ = dec.run(prompt, nt, effort=0.25, **kw)
+            best = max(best, 1 / dt)
+        return round(best, 1), ids
+    out = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "tokens": nt, "effort": 0.25,
+           "protocol": "best of 3 runs of 64 tokens, hipGraph replay, timed from the 3rd step; the four figures in this order, one process"}
+    out["greedy_tokens_per_s"], ids_g = tps()
+    out["sampled_top_k_40_temperature_0.8_tokens_per_s"], ids_a = tps(sampling=Sampling(temperature=0.8, top_k=40, seed=1))
+    out["sampled_top_k_64_top_p_0.9_tokens_per_s"], ids_b = tps(sampling=Sampling(temperature=1.0, top_k=64, top_p=0.9, seed=1))
+    out["greedy_again_tokens_per_s"], ids_g2 = tps()
+    greedy = (out["greedy_tokens_per_s"] + out["greedy_again_tokens_per_s"]) / 2
+    out["greedy_run_to_run"] = round(out["greedy_again_tokens_per_s"] / out["greedy_tokens_per_s"] - 1, 4)
+    out["sampled_top_k_40_vs_greedy_mean"] = round(out["sampled_top_k_40_temperature_0.8_tokens_per_s"] / greedy - 1, 4)
+    out["sampled_top_k_64_vs_greedy_mean"] = round(out["sampled_top_k_64_top_p_0.9_tokens_per_s"] / greedy - 1, 4)
+    out["greedy_runs_agree"] = ids_g == ids_g2
+    out["sampled_runs_leave_the_greedy_text"] = ids_a != ids_g and ids_b != ids_g
+    # the closing kernels alone, on the last step's logits
+    g, lib = dec.g, effort_amd.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    tok, pos = torch.zeros(1, dtype=torch.int32, device=b.dev), torch.zeros(1, dtype=torch.int32, device=b.dev)
+    n = model.cfg.vocab
+
+    def launch_argmax():
+        g._bind_stream()                                                         # (inside a capture: the capture's stream)
+        g.check(lib.effort_argmax(g.ctx, p(dec.logits), n, p(tok), p(pos), None, 0), "argmax")
+
+    def launch_sample():
+        g._bind_stream()
+        g.check(lib.effort_sample(g.ctx, p(dec.logits), n, p(dec.sample_params), p(tok), p(pos), None, 0, None, None), "sample")
+
+    def us_per_launch(fn, per_graph, replays):
+        g._bind_stream()
+        fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            for _ in range(per_graph):
+                fn()
+        g._bind_stream()
+        for _ in range(20):
+            gr.replay()
+        best = float("inf")
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(replays):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) * 1e3 / (replays * per_graph))
+        return round(best, 2)
+    k = {"n": n, "protocol": "device events around replays of a captured graph, best of 3 windows; one launch per graph x 512 replays "
+                            "(graph-launch overhead included, the same for both kernels), and 64 launches per graph x 32 replays"}
+    for name, sm in (("sample_top_k_40_temperature_0.8", Sampling(temperature=0.8, top_k=40, seed=1)),
+                     ("sample_top_k_64_top_p_0.9", Sampling(temperature=1.0, top_k=64, top_p=0.9, seed=1))):
+        dec.set_sampling(sm)
+        k[name] = {"us_per_launch_one_per_graph": us_per_launch(launch_sample, 1, 512), "us_per_launch_64_per_graph": us_per_launch(launch_sample, 64, 32)}
+    k["argmax"] = {"us_per_launch_one_per_graph": us_per_launch(launch_argmax, 1, 512), "us_per_launch_64_per_graph": us_per_launch(launch_argmax, 64, 32)}
+    out["closing_kernel"] = k
+    res["decode_sampled"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r08_decode_sampled.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -324,7 +414,7 @@ def layer_latency(b, res):
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
-       "decode_mixtral": decode_mixtral}
+       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled}
 
 
 def main():

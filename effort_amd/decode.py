@@ -4,10 +4,12 @@ models (the caller of the hot path).
 One token step = per layer: rmsNorm * attnNorm -> wq | wk | wv (ONE grouped bucketMul launch: three independent calls on
 the same input) -> rope + 4x kv repeat + cache -> scores / softmax / weighted sum -> wo -> residual + rmsNorm * ffnNorm
 -> w1 | w3 (one grouped launch) -> silu -> w2 -> residual; then the output norm, the dense LM head (``basicMul``,
-runNetwork.swift:222) and a greedy pick.  The glue runs in the HIP kernels of effort_amd/csrc/decode.hip through the C
-ABI; the token position and the current token id live in device memory, so a whole step is captured once into a hipGraph
-and replayed per token -- no host work, no per-kernel launch gaps (the reference spends ~15 ms/token in such gaps,
-runNetwork.swift:91-103).  torch is used for buffers and graph capture only.
+runNetwork.swift:222) and a greedy or sampled pick.  ``Decoder.token_step`` is that walk, written once for FP16, Q4, Mixtral
+and column-sharded models; its docstring says who multiplies, which glue folds into the multiplies and how many launches a
+layer makes under which settings, and ``Decoder``'s where ``fused_attention`` applies.  The glue runs in the HIP kernels of
+effort_amd/csrc/decode.hip through the C ABI; the token position and the current token id live in device memory, so a whole
+step is captured once into a hipGraph and replayed per token -- no host work, no per-kernel launch gaps (the reference
+spends ~15 ms/token in such gaps, runNetwork.swift:91-103).  torch is used for buffers and graph capture only.
 
 ``dense=True`` routes every projection through ``basicMul`` (rocBLAS GEMV on the f16 cores): the baseline the
 reference compares against (``effort`` 100 % vs dense, KL divergence of the logits).
@@ -169,13 +171,18 @@ Q4_FUSED_DEFAULT = ()
 
 
 class Decoder:
-    """State of one sequence (the globals of main.swift:78-140: h, xq, KV caches, scores ...) + the token step."""
+    """State of one sequence (the globals of main.swift:78-140: h, xq, KV caches, scores ...) + the token step.
+
+    ``fused_attention``: True -- rope, the cache write and the attention of a layer are one launch (effort_rope_attention).  False
+    -- two (effort_rope_kv + effort_attention), but ONLY in the steps that fold no glue on an FP16 model, and in every ``dense=True``
+    step: a step with any of norm / gate / resid folded, a column-sharded step and every effort step of a model with Q4 or core-only
+    bundles keep the one launch whatever this says."""
 
     def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
                  world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False):
         cfg = self.cfg = model.cfg
-        # A model with Q4 or core-only bundles (Model.random(q4=True) / Model.load(q4=True)): token_step dispatches per BUNDLE
-        # (_token_step_bundles); an all-FP16 model takes exactly the paths below.
+        # A model with Q4 or core-only bundles (Model.random(q4=True) / Model.load(q4=True)).  token_step dispatches every multiply per
+        # BUNDLE; an all-FP16 model is the case in which every bundle is a bucketed FP16 one.
         self.mixed = any(ew.q4 or not ew.bucketsLoaded for L in model.layers for ew in (L.wq, L.wk, L.wv, L.wo, L.w1, L.w2, L.w3))
         if self.mixed and (cfg.numExperts > 1 or any(L.ffnGate is not None for L in model.layers)):
             raise ValueError("Decoder: Q4 decode is Mistral only (numExperts == 1; the reference's Q4 converter writes no Mixtral model)")
@@ -190,7 +197,7 @@ class Decoder:
             fused_glue = Q4_FUSED_DEFAULT if self.mixed else True
         # (Round 4's `chain=True` -- a layer's dependent multiplies as ONE launch of resident workgroups -- measured 252 against 308
         #  tokens/s and lives on branch `chain-launch`: DESIGN.md 4.5.)
-        self.fused_attention = bool(fused_attention)      # rope + cache + attention in one launch per layer (else two)
+        self.fused_attention = bool(fused_attention)      # rope + cache + attention in one launch per layer (else two: see the class)
         # rmsNorm, silu and the residual adds folded into the multiplies (effort_bucketmul_group_fused): 5 launches per layer
         # instead of 8.  Dense-FFN models only; the dense baseline keeps the separate glue kernels.  On by default since round 3:
         # with every operand of a prologue asked for at the top of the item (they were two more dependent round trips) and the
@@ -210,6 +217,8 @@ class Decoder:
         else:
             self.fuse = frozenset(parts)
         self.fused_glue = bool(self.fuse)
+        # Where fused_attention=False applies, by token_step's ``dense``: every dense step; an effort step of an FP16 model that folds nothing.
+        self._two_launch_attention = {True: not self.fused_attention, False: not (self.fused_attention or self.mixed or self.fused_glue)}
         self.model, self.maxTokens = model, int(maxTokens)
         dev = model.norm.device
         self.g = _gpu(dev.index)
@@ -255,7 +264,30 @@ class Decoder:
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
     def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None):
-        """``sampling``: None -- the step ends in the greedy pick (effort_argmax); a ``Sampling`` -- its settings are written to
+        """ONE walk serves every model and every setting: the embedding fetch; per layer an attention half (norm -> wq | wk | wv ->
+        rope + cache + attention -> wo -> residual) and an FFN half (norm -> w1 | w3 -> silu -> w2 -> residual, or with an ffnGate the
+        routed form: gate + top-2 -> both experts' w1 | w3 as one group of four -> both w2 as one group of two -> mix); then the closing
+        norm, the LM head and ``_pick``.  What differs between settings is decided per call:
+
+        WHO MULTIPLIES (``muls``: an input vector and the [(bundle, out, extras)] that share it).  ``dense``: ``basicMul`` on every
+        core.  Column-sharded: ``self.groups.mul`` (this rank's shards in one launch, one gather).  Otherwise per bundle, as expertMul
+        does (expertMul.swift:24-38): the bucketed Q4 bundles of the items share one launch and the bucketed FP16 ones another --
+        ``bucketMulQ4`` / ``bucketMul`` for a lone call without extras, ``bucketMulGroup`` otherwise --, and a core-only bundle (wk,
+        wv, wo of the reference's Q4 model) goes to ``basicMul``.
+
+        WHAT FOLDS into those launches (``self.fuse``; under ``dense`` nothing is bucketed, so nothing folds).  The norm prologue:
+        when "norm" is asked for, no residual is pending (a product not yet added to h is added by effort_add_rmsnorm_mul on its way:
+        "norm" folds fully only with "resid") and EVERY consumer of the normalised input is bucketed (a dense neighbour reads it from
+        memory).  The gate prologue and the residual epilogue: when asked for and the target bundle (w2; wo / w2) is bucketed.  An
+        all-FP16 model is the case "every bundle bucketed", the sharded loop the case "everything folded" with another launcher, and
+        the reference's Q4 layout folds gate + resid into w2 only.
+
+        Launches per layer: 5 with norm, gate and resid folded (wq|wk|wv, rope_attention, wo, w1|w3, w2), 8 with nothing folded (two
+        norms and the silu back); Mixtral 7 folded (wq|wk|wv, rope_attention, wo, effort_moe_route = norm + gate GEMV + top-2, the
+        group of four with the same norm as its prologue -- the same bits: both sum in add_rmsnorm_mul_kernel's order --, the group
+        of two, effort_mix2_add) and 12 unfolded.  ``fused_attention=False`` adds one where it applies (see ``Decoder``).
+
+        ``sampling``: None -- the step ends in the greedy pick (effort_argmax); a ``Sampling`` -- its settings are written to
         ``self.sample_params`` and the step ends in effort_sample; True -- effort_sample on what ``self.sample_params`` holds (how the
         step is captured: the graph reads the settings from that tensor at every replay)."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
@@ -264,139 +296,102 @@ class Decoder:
         if isinstance(sampling, Sampling):
             self.set_sampling(sampling)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
+        fn, fg, fr = (part in self.fuse and not dense for part in ("norm", "gate", "resid"))
+        bucketed = lambda *ews: not dense and all(ew.bucketsLoaded for ew in ews)   # noqa: E731
+        delta = None                                       # a product not yet added to h: the next effort_add_rmsnorm_mul adds it
 
-        def muls(v, pairs):
+        def muls(v, items):                                # items: [(ew, out, extras)]
             if dense:
-                for ew, out in pairs:
+                for ew, out, _ in items:
                     basicMul(v, ew.core, out)
-            elif len(pairs) == 1:
-                bucketMul(v, pairs[0][0], None, pairs[0][1], effort)
-            else:
-                bucketMulGroup([(v, ew, None, out, effort) for ew, out in pairs])
+                return
+            if self.sharded:
+                return self.groups.mul(v, items, effort)
+            for q4 in (True, False):
+                calls = [(v, ew, None, out, effort, x) for ew, out, x in items if ew.bucketsLoaded and ew.q4 == q4]
+                if len(calls) == 1 and not calls[0][5]:
+                    (bucketMulQ4 if q4 else bucketMul)(v, calls[0][1], None, calls[0][3], effort)
+                elif calls:
+                    bucketMulGroup(calls)
+            for ew, out, x in items:
+                if not ew.bucketsLoaded:
+                    assert not x, "glue folds into bucketed multiplies only"
+                    basicMul(v, ew.core, out)
 
-        ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
-        delta = None
-        if self.mixed and not dense:
-            return self._token_step_bundles(effort, sampled)
-        if self.sharded and not dense:
-            G = self.groups
-            for n, L in enumerate(m.layers):
-                an, fnw = {"norm": L.attnNorm}, {"norm": L.ffnNorm}
-                G.mul(self.h, [(L.wq, self.xq_temp, an), (L.wk, self.xk_temp, an), (L.wv, self.xv_temp, an)], effort)      # :121-134
-                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
-                                             _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
-                                             C.c_float(cfg.ropeBase)), "rope_attention")
-                G.mul(self.attnOutput, [(L.wo, self.h, {"resid": self.h})], effort)                                     # :170-172, in place on h
-                G.mul(self.h, [(L.w1, self.x1, fnw), (L.w3, self.x3, fnw)], effort)                                      # :173-179
-                G.mul(self.x1, [(L.w2, self.h, {"gate": self.x3, "resid": self.h})], effort)                             # :181-183, in place on h
-            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
-            basicMul(self.outNormed, m.output, self.logits)                                           # :222 (replicated: every rank picks the same token)
-            self._pick(sampled)
-            return
-        if self.fused_glue and self.moe and not dense:
-            # Mixtral, everything folded: 7 launches per layer.  The routing reads h and ffnNorm itself, the experts' w1|w3 take the
-            # same norm as their prologue (the same bits: both sum in add_rmsnorm_mul_kernel's order), and the mix lands on h.
+        def rmsnorm(w, out):                               # h += delta; out = rmsNorm(h) * w
+            nonlocal delta
+            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(w), _p(out), cfg.stateDim), "rmsnorm")
+            delta = None
+
+        def normed(w, out, *ews):                          # (input, extras) of the multiplies ``ews`` that read rmsNorm(h) * w
+            if fn and delta is None and bucketed(*ews):
+                return self.h, {"norm": w}
+            rmsnorm(w, out)
+            return out, None
+
+        def gated(x1, x3, x2, ew):                         # (input, extras) of the multiply that reads silu(x1) * x3
+            if fg and bucketed(ew):
+                return x1, {"gate": x3}
+            ck(lib.effort_silu_mul(g.ctx, _p(x1), _p(x3), _p(x2), cfg.hiddenDim), "silu")
+            return x2, {}
+
+        def add_product(ew, v, extras, out):               # h += ew(v): the launch's epilogue, in place on h -- else pending in out
+            nonlocal delta
+            if fr and bucketed(ew):
+                muls(v, [(ew, self.h, dict(extras, resid=self.h))])
+            else:
+                muls(v, [(ew, out, extras or None)])
+                delta = out
+
+        def attention(n):                                  # xq_temp, xk_temp, xv_temp -> attnOutput, the caches at pos written
+            kc, vc, rope = _p(self.kCache[n]), _p(self.vCache[n]), C.c_float(cfg.ropeBase)
+            if self._two_launch_attention[bool(dense)]:
+                ck(lib.effort_rope_kv(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
+                                      cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv")
+                ck(lib.effort_attention(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.headDim,
+                                        self.maxTokens), "attention")
+            else:
+                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), kc, vc, _p(self.pos),
+                                             _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_attention")
+
+        def routed_ffn(L, v, x):
+            # Mixtral (:185-199): dense gate -> top-2 experts -> softmax of the two; the expert numbers stay on the device (expNo).
+            # Folded (all or nothing, see __init__), the routing reads h and ffnNorm itself and the mix lands on h.
+            nonlocal delta
             e0, e1 = self.gateIdxs[0:1], self.gateIdxs[1:2]
-            for n, L in enumerate(m.layers):
-                an, fnw = {"norm": L.attnNorm}, {"norm": L.ffnNorm}
-                bucketMulGroup([(self.h, L.wq, None, self.xq_temp, effort, an), (self.h, L.wk, None, self.xk_temp, effort, an),
-                                (self.h, L.wv, None, self.xv_temp, effort, an)])                                       # :121-134
-                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
-                                             _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
-                                             C.c_float(cfg.ropeBase)), "rope_attention")
-                bucketMulGroup([(self.attnOutput, L.wo, None, self.h, effort, {"resid": self.h})])                   # :170-172, h += wo(attn)
+            if x:
                 ck(lib.effort_moe_route(g.ctx, _p(self.h), _p(L.ffnNorm), _p(L.ffnGate), cfg.stateDim, cfg.numExperts, None,
                                         _p(self.gateIdxs), _p(self.gateVals)), "moe_route")                         # :173-175,185-189
-                bucketMulGroup([(self.h, L.w1, e0, self.x1, effort, fnw), (self.h, L.w3, e0, self.x3, effort, fnw),
-                                (self.h, L.w1, e1, self.x1b, effort, fnw), (self.h, L.w3, e1, self.x3b, effort, fnw)])
-                bucketMulGroup([(self.x1, L.w2, e0, self.ffnOut, effort, {"gate": self.x3}),
-                                (self.x1b, L.w2, e1, self.ffnOutB, effort, {"gate": self.x3b})])
-                ck(lib.effort_mix2_add(g.ctx, _p(self.h), _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), cfg.stateDim), "mix2_add")   # :190-199
-            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), None, _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
-            basicMul(self.outNormed, m.output, self.logits)                                           # :222
-            self._pick(sampled)
-            return
-        if self.fused_glue and not dense:
-            fn, fg, fr = "norm" in self.fuse, "gate" in self.fuse, "resid" in self.fuse
-            for n, L in enumerate(m.layers):
-                if fn and delta is None:                       # (a pending residual add needs the glue kernel: "norm" folds fully only with "resid")   :121-134
-                    bucketMulGroup([(self.h, L.wq, None, self.xq_temp, effort, {"norm": L.attnNorm}),
-                                    (self.h, L.wk, None, self.xk_temp, effort, {"norm": L.attnNorm}),
-                                    (self.h, L.wv, None, self.xv_temp, effort, {"norm": L.attnNorm})])
-                else:
-                    ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(L.attnNorm), _p(self.h_norm), cfg.stateDim), "rmsnorm")
-                    delta = None
-                    muls(self.h_norm, [(L.wq, self.xq_temp), (L.wk, self.xk_temp), (L.wv, self.xv_temp)])
-                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
-                                             _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
-                                             C.c_float(cfg.ropeBase)), "rope_attention")
-                if fr:
-                    bucketMulGroup([(self.attnOutput, L.wo, None, self.h, effort, {"resid": self.h})])         # :170-172, h += wo(attn)
-                    d2 = None
-                else:
-                    muls(self.attnOutput, [(L.wo, self.attnFfnOut)])
-                    d2 = self.attnFfnOut
-                if fn and d2 is None:
-                    bucketMulGroup([(self.h, L.w1, None, self.x1, effort, {"norm": L.ffnNorm}),              # :173-179
-                                    (self.h, L.w3, None, self.x3, effort, {"norm": L.ffnNorm})])
-                else:
-                    ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(d2), _p(L.ffnNorm), _p(self.fxn), cfg.stateDim), "rmsnorm")
-                    muls(self.fxn, [(L.w1, self.x1), (L.w3, self.x3)])
-                if fg:
-                    src, extra = self.x1, {"gate": self.x3}
-                else:
-                    ck(lib.effort_silu_mul(g.ctx, _p(self.x1), _p(self.x3), _p(self.x2), cfg.hiddenDim), "silu")
-                    src, extra = self.x2, {}
-                if fr:
-                    bucketMulGroup([(src, L.w2, None, self.h, effort, dict(extra, resid=self.h))])            # :181-183, h += w2(silu)
-                    delta = None
-                else:
-                    if extra:
-                        bucketMulGroup([(src, L.w2, None, self.ffnOut, effort, extra)])
-                    else:
-                        muls(src, [(L.w2, self.ffnOut)])
-                    delta = self.ffnOut
-            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
-            basicMul(self.outNormed, m.output, self.logits)                                           # :222
-            self._pick(sampled)
-            return
-        for n, L in enumerate(m.layers):
-            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(L.attnNorm), _p(self.h_norm), cfg.stateDim), "rmsnorm")
-            muls(self.h_norm, [(L.wq, self.xq_temp), (L.wk, self.xk_temp), (L.wv, self.xv_temp)])      # runNetwork.swift:132-134
-            if self.fused_attention:
-                ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
-                                             _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
-                                             C.c_float(cfg.ropeBase)), "rope_attention")
             else:
-                ck(lib.effort_rope_kv(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), _p(self.kCache[n]),
-                                      _p(self.vCache[n]), _p(self.pos), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, C.c_float(cfg.ropeBase)), "rope_kv")
-                ck(lib.effort_attention(g.ctx, _p(self.xq), _p(self.kCache[n]), _p(self.vCache[n]), _p(self.pos), _p(self.attnOutput),
-                                        cfg.numHeads, cfg.headDim, self.maxTokens), "attention")
-            muls(self.attnOutput, [(L.wo, self.attnFfnOut)])                                          # :170
-            ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(self.attnFfnOut), _p(L.ffnNorm), _p(self.fxn), cfg.stateDim), "rmsnorm")
-            if L.ffnGate is None:
-                muls(self.fxn, [(L.w1, self.x1), (L.w3, self.x3)])                                    # :178-179
-                ck(lib.effort_silu_mul(g.ctx, _p(self.x1), _p(self.x3), _p(self.x2), cfg.hiddenDim), "silu")
-                muls(self.x2, [(L.w2, self.ffnOut)])                                                  # :182
-                delta = self.ffnOut
-            else:
-                # Mixtral (:185-199): dense gate -> top-2 experts -> softmax of the two; the expert numbers stay on the
-                # device (expNo).  Both experts' w1|w3 share the input: ONE grouped launch of four calls; their w2 another.
-                basicMul(self.fxn, L.ffnGate, self.gateOut)
+                basicMul(v, L.ffnGate, self.gateOut)
                 ck(lib.effort_top2_softmax(g.ctx, _p(self.gateOut), cfg.numExperts, _p(self.gateIdxs), _p(self.gateVals)), "top2")
-                e0, e1 = self.gateIdxs[0:1], self.gateIdxs[1:2]
-                if dense:
-                    self._dense_experts(L, e0, e1)
-                else:
-                    bucketMulGroup([(self.fxn, L.w1, e0, self.x1, effort), (self.fxn, L.w3, e0, self.x3, effort),
-                                    (self.fxn, L.w1, e1, self.x1b, effort), (self.fxn, L.w3, e1, self.x3b, effort)])
-                    ck(lib.effort_silu_mul(g.ctx, _p(self.x1), _p(self.x3), _p(self.x2), cfg.hiddenDim), "silu")
-                    ck(lib.effort_silu_mul(g.ctx, _p(self.x1b), _p(self.x3b), _p(self.x2b), cfg.hiddenDim), "silu")
-                    bucketMulGroup([(self.x2, L.w2, e0, self.ffnOut, effort), (self.x2b, L.w2, e1, self.ffnOutB, effort)])
+            if dense:
+                self._dense_experts(L, e0, e1)
+            else:
+                bucketMulGroup([(v, L.w1, e0, self.x1, effort, x), (v, L.w3, e0, self.x3, effort, x),
+                                (v, L.w1, e1, self.x1b, effort, x), (v, L.w3, e1, self.x3b, effort, x)])
+                (a, xa), (b, xb) = gated(self.x1, self.x3, self.x2, L.w2), gated(self.x1b, self.x3b, self.x2b, L.w2)
+                bucketMulGroup([(a, L.w2, e0, self.ffnOut, effort, xa), (b, L.w2, e1, self.ffnOutB, effort, xb)])
+            if fr:
+                ck(lib.effort_mix2_add(g.ctx, _p(self.h), _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), cfg.stateDim), "mix2_add")   # :190-199
+            else:
                 ck(lib.effort_mix2(g.ctx, _p(self.ffnOut), _p(self.ffnOutB), _p(self.gateVals), _p(self.ffnMix), cfg.stateDim), "mix2")
                 delta = self.ffnMix
-        ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
-        basicMul(self.outNormed, m.output, self.logits)                                               # :222
+
+        ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
+        for n, L in enumerate(m.layers):
+            v, x = normed(L.attnNorm, self.h_norm, L.wq, L.wk, L.wv)
+            muls(v, [(L.wq, self.xq_temp, x), (L.wk, self.xk_temp, x), (L.wv, self.xv_temp, x)])        # runNetwork.swift:121-134
+            attention(n)
+            add_product(L.wo, self.attnOutput, {}, self.attnFfnOut)                                      # :170-172
+            v, x = normed(L.ffnNorm, self.fxn, L.w1, L.w3)
+            if L.ffnGate is not None:
+                routed_ffn(L, v, x)
+            else:
+                muls(v, [(L.w1, self.x1, x), (L.w3, self.x3, x)])                                        # :173-179
+                add_product(L.w2, *gated(self.x1, self.x3, self.x2, L.w2), self.ffnOut)                  # :181-183
+        rmsnorm(m.norm, self.outNormed)
+        basicMul(self.outNormed, m.output, self.logits)                                                  # :222 (sharded: replicated, every rank picks the same token)
         self._pick(sampled)
 
     def _pick(self, sampled: bool):
@@ -433,70 +428,6 @@ class Decoder:
                 if want == i:
                     return j + 1
         return 99
-
-    def _token_step_bundles(self, effort: float, sampled: bool = False):
-        """The token step of a model whose bundles are not all FP16, dispatched per bundle as expertMul does (expertMul.swift:24-38):
-        a Q4 bundle with buckets -> the Q4 multiply, a core-only bundle -> dense basicMul, an FP16 bundle -> bucketMul.  Bundles of
-        one kind that share an input share ONE group launch (w1|w3).  Glue folds into a launch where the BUNDLES allow it: the norm
-        prologue needs every consumer of the normalised input bucketed (a dense neighbour reads it from memory) and no pending
-        residual delta; the residual epilogue and the gate need a bucketed wo / w2.  The reference's Q4 layout (wk, wv, wo dense)
-        therefore folds gate + resid into w2 only; a model whose wo is bucketed too folds the norms as well."""
-        cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
-        ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
-        fn, fg, fr = "norm" in self.fuse, "gate" in self.fuse, "resid" in self.fuse
-        bucketed = lambda *ews: all(ew.bucketsLoaded for ew in ews)                 # noqa: E731
-
-        def muls(v, items):                                # items: [(ew, out, extras)]
-            for q4 in (True, False):
-                calls = [(v, ew, None, out, effort, x) for ew, out, x in items if ew.bucketsLoaded and ew.q4 == q4]
-                if len(calls) == 1 and not calls[0][5]:
-                    (bucketMulQ4 if q4 else bucketMul)(v, calls[0][1], None, calls[0][3], effort)
-                elif calls:
-                    bucketMulGroup(calls)
-            for ew, out, x in items:
-                if not ew.bucketsLoaded:
-                    assert not x, "glue folds into bucketed multiplies only"
-                    basicMul(v, ew.core, out)
-
-        ck(lib.effort_fetch_row(g.ctx, _p(m.tokEmbeddings), _p(self.tokId), _p(self.h), cfg.stateDim), "fetch_row")
-        delta = None
-        for n, L in enumerate(m.layers):
-            qkv = ((L.wq, self.xq_temp), (L.wk, self.xk_temp), (L.wv, self.xv_temp))
-            if fn and delta is None and bucketed(L.wq, L.wk, L.wv):                                   # :121-134
-                muls(self.h, [(ew, out, {"norm": L.attnNorm}) for ew, out in qkv])
-            else:
-                ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(L.attnNorm), _p(self.h_norm), cfg.stateDim), "rmsnorm")
-                delta = None
-                muls(self.h_norm, [(ew, out, None) for ew, out in qkv])
-            ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.kCache[n]), _p(self.vCache[n]),
-                                         _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens,
-                                         C.c_float(cfg.ropeBase)), "rope_attention")
-            if fr and bucketed(L.wo):
-                muls(self.attnOutput, [(L.wo, self.h, {"resid": self.h})])                           # :170-172, h += wo(attn)
-                d2 = None
-            else:
-                muls(self.attnOutput, [(L.wo, self.attnFfnOut, None)])
-                d2 = self.attnFfnOut
-            if fn and d2 is None and bucketed(L.w1, L.w3):                                            # :173-179
-                muls(self.h, [(L.w1, self.x1, {"norm": L.ffnNorm}), (L.w3, self.x3, {"norm": L.ffnNorm})])
-            else:
-                ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(d2), _p(L.ffnNorm), _p(self.fxn), cfg.stateDim), "rmsnorm")
-                muls(self.fxn, [(L.w1, self.x1, None), (L.w3, self.x3, None)])
-            extra = {}
-            if fg and bucketed(L.w2):
-                src, extra = self.x1, {"gate": self.x3}
-            else:
-                ck(lib.effort_silu_mul(g.ctx, _p(self.x1), _p(self.x3), _p(self.x2), cfg.hiddenDim), "silu")
-                src = self.x2
-            if fr and bucketed(L.w2):
-                muls(src, [(L.w2, self.h, dict(extra, resid=self.h))])                               # :181-183, h += w2(silu), in place
-                delta = None
-            else:
-                muls(src, [(L.w2, self.ffnOut, extra or None)])
-                delta = self.ffnOut
-        ck(lib.effort_add_rmsnorm_mul(g.ctx, _p(self.h), _p(delta), _p(m.norm), _p(self.outNormed), cfg.stateDim), "rmsnorm")
-        basicMul(self.outNormed, m.output, self.logits)                                               # :222
-        self._pick(sampled)
 
     def _dense_experts(self, L, e0, e1):
         """Dense baseline of the routed FFN: basicMul on the picked expert of each stack of cores, the expert number read on the device

@@ -43,16 +43,10 @@
 
 namespace effort {
 
-#ifndef EFFORT_KBATCH
-#define EFFORT_KBATCH 16
-#endif
-constexpr int kBatch = EFFORT_KBATCH;   // bucket rows per batch; two batches in flight per wave
-#ifndef EFFORT_KBATCH4
-#define EFFORT_KBATCH4 8
-#endif
+constexpr int kBatch = 16;   // bucket rows per batch; two batches in flight per wave
 // 8-byte pieces (E = 4) fly 8 per batch: the same bytes in flight per wave as 16 4-byte pieces, in half the registers (the
 // freed ones hold the next item's staged loads across the streaming phase)
-template <int E> __host__ __device__ constexpr int batch_rows() { return E >= 4 ? EFFORT_KBATCH4 : kBatch; }
+template <int E> __host__ __device__ constexpr int batch_rows() { return E >= 4 ? 8 : kBatch; }
 constexpr int kRounds = 16;  // selection rounds of NT candidate slots a workgroup can run: slots per slice <= kRounds * NT
 
 // Ablation builds for profiling (-DEFFORT_ABLATE_NOSCATTER=1 / -DEFFORT_ABLATE_NOLOAD=1); never shipped.
@@ -65,9 +59,7 @@ constexpr int kRounds = 16;  // selection rounds of NT candidate slots a workgro
 
 // Register budget of the 8-wave (and smaller) instantiations, as waves per SIMD the kernel must fit.  4 = 128 VGPRs
 // (two 8-wave workgroups per CU).  Measured: forcing 6 (80 VGPRs, three per CU; hipcc spills 64 B) is 5-15 % SLOWER.
-#ifndef EFFORT_MIN_WAVES_PER_EU
-#define EFFORT_MIN_WAVES_PER_EU 4
-#endif
+constexpr int kMinWavesPerEU = 4;
 
 // Cache policy of the bucket-row stream: NON-TEMPORAL (aux bit 1, `nt`; -DEFFORT_ROW_AUX=0 builds the temporal policy).  A kept row is
 // read once per call and a model's weights are tens of times the chip's caches (Mistral-7B at 25 % effort reads 3.5 GB per token against
@@ -89,20 +81,12 @@ constexpr int kRounds = 16;  // selection rounds of NT candidate slots a workgro
 #endif
 constexpr int kRowAux = EFFORT_ROW_AUX;
 // (Q4: the outlier entries are read once per call too, but nt on THEIR loads measured slower -- 16 calls per launch 58.8 -> 63.7 us, 32:
-//  100.4 -> 106.3 -- and stays off: -DEFFORT_OL_NT=1 builds it.)
-#ifndef EFFORT_OL_NT
-#define EFFORT_OL_NT 0
-#endif
-#if EFFORT_OL_NT
-#define EFFORT_OL_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define EFFORT_OL_LOAD(p) (*(p))
-#endif
+//  100.4 -> 106.3 -- and stays off.)
 // PERSIST (template parameter of the kernel and of mul_item) = false: the LEAN instantiation for PLAIN grids -- one item per
 // workgroup, no item queues, no cutoff jobs, no staging of a next item, no stamps or ablation switches.  It is the same kernel
 // with those compiled out: 4300 instead of 8000 instructions and 116 instead of 128 VGPRs.  A plain grid's workgroup runs its
 // path once and every instruction on it is four cycles of the call's dependent chain (a wave issues one instruction per four
-// cycles; A/B with EFFORT_PAD_TEST: 1000 executed s_nop = +1.65 us per launch, 24 KB of code nobody executes = nothing), so the
+// cycles; A/B with padding: 1000 executed s_nop = +1.65 us per launch, 24 KB of code nobody executes = nothing), so the
 // polls, flag tests and queue handling a plain grid does not need were a microsecond of every lone call: 22.8 -> 21.5 us, the
 // decode loop 267 -> 290 tokens/s (A/B on one box).  The generic instantiation serves persistent launches and the debug modes.
 #define GA_PERSISTENT(ga) (PERSIST ? (ga).persistent : 0u)
@@ -111,11 +95,11 @@ constexpr int kRowAux = EFFORT_ROW_AUX;
 // stamps, no per-item trace, no ablation switches in ANY instantiation -- the macros below are constants and the code behind them is
 // gone (tests/test_abi.py disassembles the library: no s_memrealtime in bucket_mul_kernel).  libeffort_hip_lab.so (-DEFFORT_LAB) is
 // the lab bench the tools load (EFFORT_HIP_LIB=lab): the generic instantiation then carries the stamps / trace / ablation paths, and
-// the A/B macros (EFFORT_PAD_TEST, EFFORT_CUT_FINE, EFFORT_ABLATE_*, EFFORT_NO_TOUCH, ...) are accepted.  Round 6 A/B of the two
+// the A/B macros (EFFORT_CUT_FINE, EFFORT_LEAN_STAMPS, EFFORT_ABLATE_*) are accepted.  Round 6 A/B of the two
 // builds on the throughput launches: profiles/r06_ab_product_only.txt.
 #ifndef EFFORT_LAB
 #define EFFORT_PRODUCT_ONLY 1
-#if defined(EFFORT_PAD_TEST) || defined(EFFORT_CUT_FINE) || defined(EFFORT_NO_TOUCH) || defined(EFFORT_NO_STAMPS) || EFFORT_ABLATE_NOSCATTER || EFFORT_ABLATE_NOLOAD
+#if defined(EFFORT_CUT_FINE) || defined(EFFORT_LEAN_STAMPS) || EFFORT_ABLATE_NOSCATTER || EFFORT_ABLATE_NOLOAD
 #error "lab switches need -DEFFORT_LAB (they belong in libeffort_hip_lab.so / build/variants, never in the shipped library)"
 #endif
 #endif
@@ -136,6 +120,11 @@ constexpr bool kProductOnly = false;
 #define GA_TSTAMP(ga) (PERSIST ? (ga).tstamp : nullptr)
 #define GA_ABLATE(ga) (PERSIST ? (ga).ablate : 0u)
 #define GA_TRACE(ga) (PERSIST ? (ga).trace : 0u)
+#endif
+#ifdef EFFORT_LEAN_STAMPS
+constexpr bool kLeanStamps = true;
+#else
+constexpr bool kLeanStamps = false;
 #endif
 constexpr uint32_t kMaxLdsBytes = 160u * 1024u - 1024u;     // dynamic LDS a launch may ask for: a gfx950 CU's 160 KB less the kernel's static words (rounded up generously)
 constexpr int kSc1 = 16;     // buffer aux bit: sc1 = write-through store / L1-bypassing load (cross-XCD visible)
@@ -369,7 +358,7 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     int tid0 = threadIdx.x;
     asm volatile("" : "+v"(tid0));      // opaque per item: keeps the compiler from hoisting every tid-derived value out of the item loop (+50 VGPRs)
     const int tid = tid0, lane = tid & 63;
-#if defined(EFFORT_NO_STAMPS) || defined(EFFORT_CUT_FINE)
+#ifdef EFFORT_CUT_FINE
     const bool wstamp = false;
 #else
     const bool wstamp = GA_TSTAMP(ga) && tid == 0;
@@ -479,16 +468,15 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     float rawn[VPT]; uint32_t auxc[VPT]; uint32_t auxS = 0u;
     uint32_t auxS1 = 0u;                                          // (Q4 stages TWO inputs of the slice per thread, stage_issue: vAux of the second)
     const bool preAny = FUSED && pre != (uint32_t)kPreNone;       // uniform
-    const bool needCutEarly = fused && cachedCall != ci;          // (= needCut below)
 #pragma unroll
     for (int i = 0; i < VPT; i++) { rawn[i] = 0.0f; auxc[i] = 0u; }
     if (preAny) {
         const bool gate = pre == (uint32_t)kPreSiluGate;
-        if (needCutEarly || !gate) {
+        if (needCut || !gate) {
 #pragma unroll
             for (int i = 0; i < VPT; i++) rawn[i] = *(a.v + tid + NT * i);
         }
-        if (needCutEarly) {
+        if (needCut) {
 #pragma unroll
             for (int i = 0; i < VPT; i++) {
                 auxc[i] = gate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + tid + NT * i)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[tid + NT * i];
@@ -502,7 +490,7 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
             auxS1 = gate ? __float_as_uint(*(reinterpret_cast<const float*>(a.vAux) + js1)) : (uint32_t)reinterpret_cast<const uint16_t*>(a.vAux)[js1];
             // Q4 with outliers: the early LDS copy of the whole input (olEarly: inDim = 4096) must hold the TRANSFORMED input, so the operands
             // of the first 4096 inputs are asked for whether or not this item evaluates the cutoff
-            if (olEarly && !needCutEarly) {
+            if (olEarly && !needCut) {
                 if (gate) {
 #pragma unroll
                     for (int i = 0; i < VPT; i++) rawn[i] = *(a.v + tid + NT * i);
@@ -697,11 +685,6 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     if (stamp) GA_TSTAMP(ga)[18] = wall_clock64();
     if (wstamp) ph[2] = wall_clock64();
 
-#if defined(EFFORT_PAD_TEST) && EFFORT_PAD_TEST == 1            // A/B: 24 KB of code nobody executes, in the middle of the kernel
-    if (ga.numCU == 0xdeadu) asm volatile(".rept 6000\n s_nop 0\n .endr" ::: "memory");
-#elif defined(EFFORT_PAD_TEST) && EFFORT_PAD_TEST == 2          // A/B: 4 KB of code everybody executes (1000 cycles by itself)
-    asm volatile(".rept 1000\n s_nop 0\n .endr" ::: "memory");
-#endif
     // ---- C. keep test (bucketMul.metal:69 / bucketMulQ4.metal:47) + compaction -------------------
     // Every thread tests its slot of each round against the means it holds in registers (FP16: all its slots belong to ONE
     // input row, whose |v| it reads once), ballots, and a wave sums its survivors; ONE LDS atomic per wave reserves that
@@ -920,7 +903,7 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     auto ol_fetch = [&](uint32_t (&ent)[kOlMerged]) {              // the entries of the next kOlMerged steps asked for (branch-free: lanes past a step's population read on into the next entries)
 #pragma unroll
         for (int u = 0; u < kOlMerged; u++) {
-            ent[u] = EFFORT_OL_LOAD((a.ol.entry + olCur) + lane);                   // (a uniform base + 4 * lane: no address arithmetic per step; the array ends in 64 entries of padding)
+            ent[u] = *((a.ol.entry + olCur) + lane);                   // (a uniform base + 4 * lane: no address arithmetic per step; the array ends in 64 entries of padding)
             olCur += (uint32_t)__popcll(__ballot(olLen > olKf + (uint32_t)u));
         }
         olKf += (uint32_t)kOlMerged;
@@ -1054,7 +1037,7 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
                     auto fetch = [&](uint32_t (&ent)[kOlBatch], uint32_t kk) {             // the entries of steps kk .. kk + kOlBatch - 1 asked for (clamped, branch-free)
 #pragma unroll
                         for (int u = 0; u < kOlBatch; u++) {
-                            ent[u] = EFFORT_OL_LOAD((ol.entry + cur) + lane);
+                            ent[u] = *((ol.entry + cur) + lane);
                             cur += (uint32_t)__popcll(__ballot(myLen > kk + (uint32_t)u));
                         }
                     };
@@ -1320,7 +1303,7 @@ __device__ __forceinline__ void cutoff_job(const GroupKArgs& ga, uint32_t ci, ch
 // (Q4 with prologues at W = 2 -- a debug geometry, 32 inputs of the cutoff per thread AND their prologue operands held beside the outlier
 //  stepper's state -- does not fit 128 VGPRs without a scratch segment: that one instantiation is budgeted two waves per SIMD)
 template <int FMT, int E, int W, bool FUSED, bool COMPACT = false, bool PERSIST = true>
-__global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <= 8 ? EFFORT_MIN_WAVES_PER_EU : 4)) void bucket_mul_kernel(const GroupKArgs ga) {
+__global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <= 8 ? kMinWavesPerEU : 4)) void bucket_mul_kernel(const GroupKArgs ga) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ uint32_t s_item;
     __shared__ unsigned long long s_next;                  // the item after the current one | the generation (item count) it was pulled in << 32: ONE word,
@@ -1328,7 +1311,6 @@ __global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <=
 #ifdef EFFORT_CUT_FINE
     if (GA_TSTAMP(ga) && blockIdx.x == 0 && threadIdx.x == 0) GA_TSTAMP(ga)[26] = clock64();
 #endif
-#ifndef EFFORT_NO_TOUCH
     // Plain grids: a workgroup's first ~10 scalar loads -- item range, call descriptor, geometry, pointers -- depend on one another,
     // and each first touch of a 64-byte line of the kernel-argument segment misses the scalar cache: the misses queue up behind one
     // another on the call's chain.  One dword of every line a small group's prologue reads (header, ranges, geometries, the first
@@ -1341,7 +1323,6 @@ __global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <=
 #pragma unroll
         for (int i = 0; i < 12; i++) asm volatile("" :: "s"(touch[i]));
     }
-#endif
 #ifdef EFFORT_CUT_FINE
 #define EFFORT_ESTAMP(i) if (GA_TSTAMP(ga) && blockIdx.x == 0 && threadIdx.x == 0) GA_TSTAMP(ga)[16 + (i)] = clock64();
 #else
@@ -1354,11 +1335,7 @@ __global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <=
     // CUs round-robin -- speed only, never correctness) start `staggerSleeps` x ~0.9 us late and the pair runs out of step from then on.  Measured, Q4 alone on the
     // chip: 32 calls per launch 109.5 -> 99.8 us at 6-12 us, 16 calls as 768 items 85.4 -> 69.0; with four launches in flight it LOSES 2-5 % (the CU is
     // busy anyway, the wait is just a wait), so the host asks for it only where launches do not overlap (api.hip: a context without lanes).
-#ifdef EFFORT_Q4_STAGGER_US                 // (lab A/B builds: a fixed delay whatever the host says)
-    const uint32_t staggerSleeps = (uint32_t)((EFFORT_Q4_STAGGER_US) * 10 / 9);
-#else
     const uint32_t staggerSleeps = ga.staggerSleeps;
-#endif
     if constexpr (PERSIST) {                    // (counted sleeps, not a clock: the shipped kernels read no clock at all)
         if (GA_PERSISTENT(ga) && staggerSleeps && blockIdx.x >= ga.numCU)
             for (uint32_t i = 0; i < staggerSleeps; i++) __builtin_amdgcn_s_sleep(32);
@@ -1449,17 +1426,35 @@ __global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <=
 }
 
 // ---- host side ------------------------------------------------------------------------------
+// The (FUSED, COMPACT, PERSIST) variants of the kernel that exist for a (FMT, E, W), ONCE: f(kernel, fused, compact, persist) for
+// each, until one fails.  bucket_mul_prepare_device and the launch selection both walk this list, so a variant cannot be launched
+// without having had its LDS attribute set.
+//   PERSIST = true   the generic instantiation: persistent launches and the debug modes, every workgroup size;
+//   PERSIST = false  the LEAN instantiation for plain grids (see GA_PERSISTENT above); built for 8-wave workgroups, the only size the heuristics choose;
+//   COMPACT          FP16 only (the row means alone, u16 per bucket row); under a persistent launch it excludes FUSED.
+template <int FMT, int E, int W, typename F>
+static hipError_t each_variant(F&& f) {
+    hipError_t err = hipSuccess;
+    auto one = [&](auto fu, auto co, auto pe) {
+        constexpr bool FU = decltype(fu)::value, CO = decltype(co)::value, PE = decltype(pe)::value;
+        if (err == hipSuccess) err = f(&bucket_mul_kernel<FMT, E, W, FU, CO, PE>, FU, CO, PE);
+    };
+    constexpr std::true_type T{}; constexpr std::false_type N{};
+    one(N, N, T); one(T, N, T);
+    if constexpr (FMT == kFp16) one(N, T, T);
+    if constexpr (W == 8) {
+        one(N, N, N); one(T, N, N);
+        if constexpr (FMT == kFp16) { one(N, T, N); one(T, T, N); }
+    }
+    return err;
+}
+
 template <int FMT, int E, int W>
 static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
     GroupKArgs ga = gaIn;
-    // plain grids of the product path (no stamps, no ablation switches) run the lean instantiation (PERSIST = false, see above);
-    // built for 8-wave workgroups, the only size the heuristics choose
+    // plain grids of the product path (no stamps, no ablation switches) run the lean instantiation
     constexpr bool kLean = W == 8;
-#ifdef EFFORT_LEAN_STAMPS
-    const bool lean = kLean && !ga.persistent && !ga.ablate;
-#else
-    const bool lean = kLean && !ga.persistent && !ga.tstamp && !ga.ablate;
-#endif
+    const bool lean = kLean && !ga.persistent && (kLeanStamps || !ga.tstamp) && !ga.ablate;
     const LdsPlan lp = ga.lp = plan_lds<FMT, E, W>(ga.geom, kMaxGeoms, lean || (kLean && kProductOnly));
     uint32_t lds = lp.total;
     if (lp.offA > 65536u && FMT == kFp16) return hipErrorInvalidValue;     // stage_issue's destinations sit below offA
@@ -1488,16 +1483,15 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
     const bool compact = (ga.split & 4u) != 0u;                   // (api.hip: persistent FP16 launches of plain calls)
     if (compact && (FMT != kFp16 || (fusedAny && !lean))) return hipErrorInvalidValue;
     const dim3 gd(grid), bd(64 * W);
-    if constexpr (kLean) {
-        if (lean && compact && fusedAny) { hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, true, true, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
-        if (lean && compact) { hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, false, true, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
-        if (lean && fusedAny) { hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, true, false, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
-        if (lean) { hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, false, false, false>), gd, bd, lds, st, ga); return hipGetLastError(); }
-    }
-    if (fusedAny) hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, true>), gd, bd, lds, st, ga);
-    else if (compact) hipLaunchKernelGGL((bucket_mul_kernel<kFp16, E, W, false, true>), gd, bd, lds, st, ga);
-    else hipLaunchKernelGGL((bucket_mul_kernel<FMT, E, W, false>), gd, bd, lds, st, ga);
-    return hipGetLastError();
+    // the generic instantiation ignores the compact bit under a prologue / residual (refused above) and takes the plain means otherwise
+    bool launched = false;
+    const hipError_t err = each_variant<FMT, E, W>([&](auto kernel, bool fu, bool co, bool pe) -> hipError_t {
+        if (launched || fu != fusedAny || co != compact || pe == lean) return hipSuccess;
+        launched = true;
+        hipLaunchKernelGGL(kernel, gd, bd, lds, st, ga);
+        return hipGetLastError();
+    });
+    return err != hipSuccess ? err : launched ? hipSuccess : hipErrorInvalidValue;
 }
 
 #define EFFORT_GEOMS(X) X(16, 1) X(16, 2) X(16, 4) X(8, 1) X(8, 2) X(8, 4) X(4, 1) X(4, 2) X(4, 4) X(2, 4)
@@ -1505,71 +1499,51 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
 // Lets every instantiation of the kernel ask for up to the whole LDS of a CU as dynamic shared memory, on the CURRENT device.
 // Done once per device when its first context is created (api.hip), not lazily at launch: a function attribute belongs to a
 // device, launches may come from several threads and devices, and a launch may sit inside a hipGraph capture.
-template <int FMT, int E, int W>
-static hipError_t prepare_t() {
-    auto set = [&](const void* f) {            // (the kernel's static words come out of the same 160 KB)
+hipError_t bucket_mul_prepare_device() {
+    auto set = [](auto kernel, bool, bool, bool) -> hipError_t {            // (the kernel's static words come out of the same 160 KB)
+        const void* f = reinterpret_cast<const void*>(kernel);
         hipFuncAttributes fa;
         hipError_t e = hipFuncGetAttributes(&fa, f);
         if (e != hipSuccess) return e;
         if (fa.sharedSizeBytes > 1024u) return hipErrorInvalidValue;
         return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160u * 1024u - (uint32_t)fa.sharedSizeBytes));
     };
-    constexpr bool kLean = W == 8;
-    hipError_t err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, false>));
-    if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, false, false, false>));
-    if constexpr (FMT != kFp16) {              // Q4 with prologues / residual: generic and lean plain (COMPACT is FP16 only)
-        if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, true>));
-        if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<FMT, E, W, true, false, false>));
-    }
-    if constexpr (FMT == kFp16) {
-        if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, true>));
-        if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, false, true>));
-        if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, true, false, false>));
-        if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, false, true, false>));
-        if constexpr (kLean) if (err == hipSuccess) err = set(reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, E, W, true, true, false>));
-    }
-    return err;
-}
-hipError_t bucket_mul_prepare_device() {
     hipError_t err = hipSuccess;
-#define EFFORT_CASE(w, e) if (err == hipSuccess) err = prepare_t<kFp16, e, w>(); if (err == hipSuccess) err = prepare_t<kQ4, e, w>();
+#define EFFORT_CASE(w, e) if (err == hipSuccess) err = each_variant<kFp16, e, w>(set); if (err == hipSuccess) err = each_variant<kQ4, e, w>(set);
     EFFORT_GEOMS(EFFORT_CASE)
 #undef EFFORT_CASE
     return err;
 }
 
-template <int FMT>
-static hipError_t launch_mul_fmt(int W, int E, const GroupKArgs& a, hipStream_t st) {
-#define EFFORT_CASE(w, e) if (W == w && E == e) return launch_mul_t<FMT, e, w>(a, st);
+// f(W, E as std::integral_constant) for the workgroup geometry asked for; false if no such geometry is built
+template <typename F>
+static bool with_geom(int W, int E, F&& f) {
+#define EFFORT_CASE(w, e) if (W == w && E == e) { f(std::integral_constant<int, w>{}, std::integral_constant<int, e>{}); return true; }
     EFFORT_GEOMS(EFFORT_CASE)
 #undef EFFORT_CASE
-    return hipErrorInvalidValue;
+    return false;
 }
 
 hipError_t launch_bucket_mul(Format fmt, int W, int E, const GroupKArgs& a, hipStream_t st) {
-    return fmt == kFp16 ? launch_mul_fmt<kFp16>(W, E, a, st) : launch_mul_fmt<kQ4>(W, E, a, st);
+    hipError_t err = hipErrorInvalidValue;
+    with_geom(W, E, [&](auto w, auto e) { err = fmt == kFp16 ? launch_mul_t<kFp16, decltype(e)::value, decltype(w)::value>(a, st) : launch_mul_t<kQ4, decltype(e)::value, decltype(w)::value>(a, st); });
+    return err;
 }
 
 size_t bucket_mul_lds_bytes(Format fmt, int W, int E, const MulGeom& g, bool lean) {
-#define EFFORT_CASE(w, e)                                                                     \
-    if (W == w && E == e)                                                                     \
-        return fmt == kFp16 ? plan_lds<kFp16, e, w>(&g, 1, lean).total : plan_lds<kQ4, e, w>(&g, 1, lean).total;
-    EFFORT_GEOMS(EFFORT_CASE)
-#undef EFFORT_CASE
-    return 0;
+    size_t n = 0;
+    with_geom(W, E, [&](auto w, auto e) { n = fmt == kFp16 ? plan_lds<kFp16, decltype(e)::value, decltype(w)::value>(&g, 1, lean).total : plan_lds<kQ4, decltype(e)::value, decltype(w)::value>(&g, 1, lean).total; });
+    return n;
 }
 
 // Resident workgroups per CU the runtime grants an instantiation at a given dynamic LDS size (0: unsupported).
 int bucket_mul_occupancy(Format fmt, int W, int E, size_t ldsBytes) {
     int n = 0;
-#define EFFORT_CASE(w, e)                                                                                              \
-    if (W == w && E == e) {                                                                                            \
-        const void* f = fmt == kFp16 ? reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, e, w, false>)                  \
-                                     : reinterpret_cast<const void*>(&bucket_mul_kernel<kQ4, e, w, false>);                   \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 64 * w, ldsBytes) != hipSuccess) n = 0;                \
-    }
-    EFFORT_GEOMS(EFFORT_CASE)
-#undef EFFORT_CASE
+    with_geom(W, E, [&](auto w, auto e) {
+        const void* f = fmt == kFp16 ? reinterpret_cast<const void*>(&bucket_mul_kernel<kFp16, decltype(e)::value, decltype(w)::value, false>)
+                                     : reinterpret_cast<const void*>(&bucket_mul_kernel<kQ4, decltype(e)::value, decltype(w)::value, false>);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 64 * decltype(w)::value, ldsBytes) != hipSuccess) n = 0;
+    });
     return n;
 }
 

@@ -186,6 +186,54 @@ def test_shipped_kernels_stream_the_bucket_rows_non_temporally(hip_lib_built, tm
     assert switched >= 10, switched
 
 
+def _multiply_kernel_resources(lib_path, tmp_path):
+    """{kernel symbol: {metadata field: value}} of every bucket_mul_kernel instantiation of `lib_path` (llvm-readelf --notes on the
+    code object that llvm-objdump --offloading extracts)."""
+    import glob
+    import shutil
+    import subprocess
+    llvm = "/opt/rocm/lib/llvm/bin"
+    if not os.path.exists(os.path.join(llvm, "llvm-readelf")):
+        pytest.skip("no llvm-readelf in this image")
+    work = os.path.join(str(tmp_path), "res_" + os.path.basename(lib_path))
+    shutil.copy(lib_path, work)
+    subprocess.run([os.path.join(llvm, "llvm-objdump"), "--offloading", work], capture_output=True, cwd=str(tmp_path), check=True)
+    out = {}
+    for co in sorted(glob.glob(work + ".*gfx950")):
+        notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+        cur = {}
+        for line in notes.splitlines():           # one YAML map per kernel: `- .agpr_count: 0` opens it, `.name:` / `.symbol:` sit inside
+            m = re.match(r"^\s*(-\s+)?(\.[a-z_]+):\s*(\S.*)?$", line)
+            if not m:
+                continue
+            if m.group(1) and line.startswith("  - "):
+                cur = {}
+            cur[m.group(2)] = (m.group(3) or "").strip("'\"")
+            if m.group(2) == ".symbol" and "bucket_mul_kernel" in cur[".symbol"]:
+                out[cur[".symbol"]] = cur
+    return out
+
+
+def test_shipped_kernels_keep_their_register_budget(hip_lib_built, tmp_path):
+    """What bucket_mul.hip's comments claim of the 8-wave kernels -- "4 = 128 VGPRs (two 8-wave workgroups per CU)", "no scratch" -- read
+    from the code object's metadata: every W = 8 instantiation of the shipped library fits 128 VGPRs without a VGPR spill or a scratch
+    segment; and the library holds the 68 instantiations the launch selection and bucket_mul_prepare_device walk (each_variant over
+    EFFORT_GEOMS)."""
+    res = _multiply_kernel_resources(hip_lib_built, tmp_path)
+    assert len(res) == 68, sorted(res)
+    wide = 0
+    for sym, r in res.items():
+        m = re.search(r"bucket_mul_kernelILi(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)E", sym)
+        assert m, sym
+        if int(m.group(3)) != 8:
+            continue
+        wide += 1
+        assert int(r[".vgpr_spill_count"]) == 0, (sym, r[".vgpr_spill_count"])
+        assert int(r[".private_segment_fixed_size"]) == 0, (sym, r[".private_segment_fixed_size"])
+        assert int(r[".vgpr_count"]) <= 128, (sym, r[".vgpr_count"])
+    assert wide == 33, wide
+
+
 def test_shipped_library_has_no_measured_dead_ends(hip_lib_built):
     """What round 4 built and measured SLOWER -- chain launches, the named reducer, byte-indexed Q4 accumulators -- lives on branch
     `chain-launch`, not in the drop-in header or the shipped library; and the library loads without RCCL (multi-GPU binds it at run

@@ -721,7 +721,10 @@ def test_q4_outlier_tables(ea, oracle_cpu, inDim, outDim):
     g = ea.gpu()
     for name, ol in tables.items():
         ew = ea.ExpertWeights(dev16(buckets), devf(stats), dev16(probes), inSize=inDim, outSize=outDim, outliers=devf(ol), q4=True)
-        for tune, effort in (((0, 0, 0), 0.25), ((8, 1, 16), 0.1), ((8, 2, 24), 0.5)):
+        tunes = [((0, 0, 0), 0.25), ((8, 1, 16), 0.1), ((8, 2, 24), 0.5)]
+        if inDim == 4096:       # a share of 16 blocks on 8 waves: the stepper's stride over the blocks (16448 inputs: no accepted geometry has more blocks than waves)
+            tunes.append(((8, 4, 8), 0.25))
+        for tune, effort in tunes:
             want, n, cutoff = oracle_cpu.bucket_mul_q4(v, buckets, stats, probes, ol, inDim, outDim, effort)
             out = torch.full((outDim,), float("nan"), device=DEV)
             try:

@@ -15,6 +15,7 @@
 #include "../../include/effort_hip.h"
 #include "../../include/effort_hip_debug.h"
 #include "effort_internal.h"
+#include "lanes.h"
 #include "plan.h"
 #include "sample_device.h"
 
@@ -29,7 +30,6 @@ struct Lane {
     hipStream_t own = nullptr;        // internal stream (overlap mode); with one lane the launches go to the context's stream
     hipEvent_t done = nullptr;        // "everything enqueued on the lane so far": recorded LAZILY, when somebody is about to wait for the lane (lane_mark)
     bool dirty = false;               // launches were enqueued on `own` since `done` was last recorded
-    unsigned long long capId = 0;     // the hipGraph capture the lane's pending launches were enqueued in (0: none -- real work on the queue)
     float* d_cutoff = nullptr;        // BucketMul.cutoff
     uint32_t* d_count = nullptr;      // dispatch.size
     float* d_slabs = nullptr;         // partial tiles (replaces tmpMulVec)
@@ -38,21 +38,16 @@ struct Lane {
     uint32_t* d_queue = nullptr;      // item queues of persistent launches
     // where each call of the lane's last (group) launch keeps its per-slice counts; slices == 0: dispatch.size is d_count
     uint32_t lastCalls = 1, lastSliceOff[effort::kMaxGroup] = {0}, lastSlices[effort::kMaxGroup] = {0};
-    // address ranges the launches enqueued since the last join read / write (hazard check of the next launch)
-    struct Range { uintptr_t lo, hi; };
-    std::vector<Range> reads, writes;
-    bool pending = false;
 };
 
 struct effort_ctx {
-    static constexpr int kMaxLanes = 4;
+    static constexpr int kMaxLanes = effort::kMaxLanes;
     int device = 0;
     hipStream_t stream = nullptr;
     int numCU = 256;
     Lane lane[kMaxLanes];
-    int nLanes = 1, lastLane = 0, nextLane = 0;
-    int busyStreak = 0;               // overlap mode: consecutive launches of a dependent chain that found the context's stream "busy" (see the lane choice)
-    bool migrated = false;            // ... and the chain was moved to another lane for it (once between joins)
+    LaneBook book;                    // overlap mode: which lanes hold launches nobody waited for yet, and the ranges they touch (lanes.h)
+    int lastLane = 0;
     hipEvent_t forkEv = nullptr;      // overlap mode: "everything enqueued on the context's stream so far"
     size_t slabBytes = 0;
     uint32_t* d_blockScratch = nullptr;
@@ -65,7 +60,6 @@ struct effort_ctx {
     int persistent = -1;              // workgroups per CU of group launches: -1 heuristic, 0 plain grid, R > 0 persistent
     static constexpr uint32_t kMaxTiles = 1024, kMaxSlices = 4096;
     static constexpr size_t kSlabBytes = (size_t)64 << 20;   // a lane's partial-tile scratch
-    static constexpr size_t kMaxRanges = 1024;   // address ranges a lane records between joins (do_group)
     unsigned long long* d_tstamp = nullptr;   // device-clock stamps of the multiply kernel (timing mode)
     double wallClockKHz = 100000.0;
     rocblas_handle blas = nullptr;
@@ -89,7 +83,7 @@ struct effort_ctx {
 struct effort_w {
     effort_ctx* ctx = nullptr;
     Format fmt = kFp16;
-    const uint16_t* buckets = nullptr;    // what the multiply reads: the caller's buffer, or `aligned`
+    const uint16_t* buckets = nullptr;    // what the multiply streams: the caller's buffer, or `aligned`
     const uint16_t* bucketsSrc = nullptr; // the caller's buffer (borrowed)
     uint16_t* aligned = nullptr;          // own copy with rows padded to whole 128-byte lines (effort_weights_align_rows)
     uint32_t rowPitch = 0;                // bytes between rows of `buckets`
@@ -235,10 +229,9 @@ extern "C" effort_ctx* effort_create(int device, void* stream) {
 }
 
 // ---- lanes: independent launches of one context in flight together (effort_set_overlap) -------------------------
-// The stream a launch of lane i goes to.
-static hipStream_t lane_stream(effort_ctx* c, int i) { return c->nLanes > 1 ? c->lane[i].own : c->stream; }
-// The lane's `done` event, brought up to date.  An event per launch made a chain of dependent lone calls -- which the hazard
-// analysis keeps on ONE lane, in order -- pay an event packet between every two kernels (the reference's own timing loop,
+// The scheduler (lanes.h: c->book) decides; what follows issues the HIP calls its answers call for.
+// The lane's `done` event, brought up to date.  An event per launch made a chain of dependent lone calls -- which the scheduler
+// keeps on ONE lane, in order -- pay an event packet between every two kernels (the reference's own timing loop,
 // benchmarks/benchmark.swift:245-257: 30.1 us per call with lanes against 22.8 without, after the fork was already skipped on an
 // idle stream); recorded only where something waits for the lane -- a join, or a launch on another lane that depends on it -- the
 // chain is back-to-back kernels on the lane's stream and nothing else.
@@ -248,6 +241,15 @@ static hipError_t lane_mark(Lane& L) {
     if (e == hipSuccess) L.dirty = false;
     return e;
 }
+// `st` waits for everything enqueued on the lanes of `set` so far.
+static hipError_t wait_for_lanes(effort_ctx* c, hipStream_t st, uint32_t set) {
+    for (int i = 0; i < effort_ctx::kMaxLanes; i++) if (set >> i & 1u) {
+        hipError_t e = lane_mark(c->lane[i]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, c->lane[i].done, 0);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 // The capture the context's stream is in (0: none).
 static unsigned long long capture_of(hipStream_t st) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -255,111 +257,53 @@ static unsigned long long capture_of(hipStream_t st) {
     if (hipStreamGetCaptureInfo(st, &cap, &id) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return cap == hipStreamCaptureStatusActive ? (id ? id : ~0ull) : 0ull;
 }
-// Lanes and hipGraph captures.  A lane's pending launches are either real work on its queue or nodes of ONE capture, the one its fork
-// edge came from (Lane::capId).  Two mixtures cannot be ordered and are refused / cleaned up here instead of surfacing as a HIP error in the
-// middle of a launch: (a) real work pending when the context's stream is capturing -- the capture would have to wait on an event recorded
-// outside it, which stream capture forbids: the caller joins BEFORE beginning the capture (returns false, c->err says so); (b) nodes of a
-// capture that has ended (or of another one): the graph's own edges order them; the bookkeeping is dropped.
+// The capture rule (LaneBook::match_capture): refused with a message instead of surfacing as a HIP error in the middle of a launch.
 static bool lanes_match_capture(effort_ctx* c, unsigned long long now) {
-    for (int i = 0; i < c->nLanes; i++) {
-        Lane& L = c->lane[i];
-        if (!L.pending || L.capId == now) continue;
-        if (L.capId == 0) {
-            snprintf(c->err, sizeof(c->err), "lanes hold launches enqueued BEFORE this hipGraph capture began: call effort_join (or effort_sync) before beginning the capture");
-            return false;
-        }
-        L.pending = false; L.dirty = false; L.capId = 0; L.reads.clear(); L.writes.clear();
-    }
+    uint32_t dropped = 0;
+    if (!c->book.match_capture(now, &dropped)) { snprintf(c->err, sizeof(c->err), "%s", kLanesPendingBeforeCapture); return false; }
+    for (int i = 0; i < effort_ctx::kMaxLanes; i++) if (dropped >> i & 1u) c->lane[i].dirty = false;
     return true;
 }
 // The context's stream waits for every lane's launches; from here on the context's stream order covers them.
 static int join_lanes(effort_ctx* c) {
-    if (c->nLanes <= 1) return EFFORT_OK;
-    bool any = false;
-    for (int i = 0; i < c->nLanes; i++) any = any || c->lane[i].pending;
-    if (any && !lanes_match_capture(c, capture_of(c->stream))) return EFFORT_ERR_ARG;
-    for (int i = 0; i < c->nLanes; i++) {
-        Lane& L = c->lane[i];
-        if (!L.pending) continue;
-        hipError_t e = lane_mark(L);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, L.done, 0);
-        if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "join: %s", hipGetErrorString(e)); return EFFORT_ERR_HIP; }
-        L.pending = false; L.capId = 0; L.reads.clear(); L.writes.clear();
+    if (c->book.pending_lanes()) {
+        if (!lanes_match_capture(c, capture_of(c->stream))) return EFFORT_ERR_ARG;
+        const hipError_t e = wait_for_lanes(c, c->stream, c->book.pending_lanes());
+        if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "join: %s", hipGetErrorString(e)); return EFFORT_ERR_HIP; }    // (the lanes stay pending)
     }
-    c->busyStreak = 0; c->migrated = false;
+    c->book.join();
     return EFFORT_OK;
 }
-static bool overlaps(const std::vector<Lane::Range>& a, const std::vector<Lane::Range>& b) {
-    for (const auto& x : a) for (const auto& y : b) if (x.lo < y.hi && y.lo < x.hi) return true;
-    return false;
-}
-// ---- which lane a group launch goes to (overlap mode) ----
-// The launch may run beside the launches in flight on the OTHER lanes unless it reads or
-// writes what one of them writes, or writes what one of them reads; then it waits for that lane (or simply joins it: a
-// lane's stream is in order).  Always ordered after everything enqueued on the context's stream before this call.
-// The lane is CHOSEN first (choose_lane) and forked (made to wait, fork_lane) only when the first kernel of the group is about to be launched:
-// a group that fails validation or finds no launch geometry has then touched no stream.  From the fork on, every way out
-// records the lane's `done` event and marks the lane pending (LaneGuard), so a later join -- in particular the join a
-// caller owes the capturing stream before it ends a hipGraph capture -- always rejoins a lane that was forked.
+// ---- a group launch on a lane (overlap mode) ----
+// The lane is CHOSEN first (choose_lane) and forked (made to wait, fork_lane) only when the first kernel of the group is about to be
+// launched: a group that fails validation or finds no launch geometry has then touched no stream.  From the fork on the lane is
+// pending, so a later join -- in particular the join a caller owes the capturing stream before it ends a hipGraph capture -- always
+// rejoins a lane that was forked.
 struct LaneChoice {
     bool laned = false;               // the launch goes to a lane's own stream (lanes > 1 and no timing / clock mode)
-    int li = 0;
-    std::vector<Lane::Range> rd, wr;  // what the launch reads / writes
-    int hazard[effort_ctx::kMaxLanes], nh = 0;        // the lanes it must follow
+    LanePick pick;
+    LaunchRanges ranges;
     unsigned long long capNow = 0;
-};
-struct LaneGuard {                                 // (see above)
-    Lane& L; bool forked = false;
-    ~LaneGuard() { if (forked) { L.dirty = true; L.pending = true; } }     // (the event itself: lane_mark, when somebody waits for the lane)
+    bool forked = false;
 };
 static int choose_lane(effort_ctx* c, LaneChoice& lc, int n, const effort_w* const* ws, const float* const* vs, const uint32_t* const* expNos,
                        float* const* outs, const void* const* vAux, const float* const* resids) {
     if (lc.laned) {
         lc.capNow = capture_of(c->stream);
         if (!lanes_match_capture(c, lc.capNow)) return EFFORT_ERR_ARG;
-        // bounded bookkeeping: a caller may enqueue arbitrarily many multiplies between joins (helpers/gpu.swift:109-119: one
-        // eval() per token); once a lane has recorded kMaxRanges ranges the lanes are JOINED -- the context's stream waits for
-        // all of them, and every later launch forks from that stream -- never forgotten
-        bool full = false;
-        for (int i = 0; i < c->nLanes; i++) full = full || c->lane[i].reads.size() + c->lane[i].writes.size() > effort_ctx::kMaxRanges;
-        if (full) { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
-        auto add = [](std::vector<Lane::Range>& v, const void* p, size_t bytes) { if (p && bytes) v.push_back({(uintptr_t)p, (uintptr_t)p + bytes}); };
-        for (int i = 0; i < n; i++) {
-            add(lc.rd, vs[i], (size_t)ws[i]->inDim * 4);
-            if (expNos && expNos[i]) add(lc.rd, expNos[i], 4);
-            if (vAux && vAux[i]) add(lc.rd, vAux[i], (size_t)ws[i]->inDim * 4);
-            if (resids && resids[i]) add(lc.rd, resids[i], (size_t)ws[i]->outDim * 4);
-            add(lc.wr, outs[i], (size_t)ws[i]->outDim * 4);
-        }
-        for (int i = 0; i < c->nLanes; i++) {
-            const Lane& L = c->lane[i];
-            if (L.pending && (overlaps(lc.rd, L.writes) || overlaps(lc.wr, L.writes) || overlaps(lc.wr, L.reads))) lc.hazard[lc.nh++] = i;
-        }
-        lc.li = lc.nh ? lc.hazard[0] : c->nextLane;
-        // A chain of dependent launches lives on ONE lane and forks from the context's stream only when that stream is busy
-        // (fork_lane).  HIP multiplexes streams over a few hardware queues, and a lane that happens to share its queue with the
-        // context's stream makes hipStreamQuery(context's stream) say "busy" while the LANE works: every link of the chain then
-        // pays the event-record-and-wait fork, +8 us per call (tools/lab/lane_probe.py with EXTRA_CONTEXTS=1: one lane of four;
-        // round 5's bench record showed it at three of five efforts).  Four busy answers in a row on a pure chain: the chain MOVES
-        // to an idle lane -- one cross-lane edge, the ordinary hazard wait below -- where the stream's answer is its own again.
-        // Once between joins: if the busy answers were true (the caller really enqueues between the calls) nothing is lost but that edge.
-        if (lc.nh == 1 && c->busyStreak >= 4 && !c->migrated) {
-            for (int k = 1; k < c->nLanes; k++) {
-                const int cand = (lc.hazard[0] + k) % c->nLanes;
-                if (!c->lane[cand].pending) { lc.li = cand; c->migrated = true; c->busyStreak = 0; break; }
-            }
-        }
-    } else if (c->nLanes > 1) {
+        if (c->book.full()) { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+        for (int i = 0; i < n; i++)
+            lc.ranges.call(vs[i], expNos ? expNos[i] : nullptr, vAux ? vAux[i] : nullptr, resids ? resids[i] : nullptr, outs[i], ws[i]->inDim, ws[i]->outDim);
+        lc.pick = c->book.pick(lc.ranges);
+    } else if (c->book.nLanes > 1) {
         { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }        // timing modes: one launch at a time, on lane 0
     }
     return EFFORT_OK;
 }
 // Before the group's first launch.
-static int fork_lane(effort_ctx* c, const LaneChoice& lc, LaneGuard& guard) {
-    if (!lc.laned || guard.forked) return EFFORT_OK;
-    Lane& L = guard.L;
-    const int li = lc.li, nh = lc.nh;
-    const int* hazard = lc.hazard;
+static int fork_lane(effort_ctx* c, LaneChoice& lc) {
+    if (!lc.laned || lc.forked) return EFFORT_OK;
+    Lane& L = c->lane[lc.pick.lane];
     // "after everything enqueued on the context's stream before this call": an event recorded there, the lane waits -- UNLESS the
     // stream is idle: then everything enqueued on it has completed and there is nothing to wait for.  That is the state of a
     // caller who enqueues multiply after multiply and evaluates once (helpers/gpu.swift:109-119; the reference's own timing
@@ -379,30 +323,11 @@ static int fork_lane(effort_ctx* c, const LaneChoice& lc, LaneGuard& guard) {
         HIP_TRY(c, hipEventRecord(c->forkEv, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(L.own, c->forkEv, 0));
     }
-    c->busyStreak = (wait && nh == 1 && hazard[0] == li) ? c->busyStreak + 1 : 0;     // (a dependent chain's link that had to fork)
-    guard.forked = true;
-    L.capId = lc.capNow;
-    // (a range the lane holds already is not recorded twice: a loop that multiplies into the same vectors over and over --
-    //  the reference's timing loop -- would otherwise grow the lists to their cap, and every call scan thousands of ranges)
-    auto add_new = [](std::vector<Lane::Range>& have, const std::vector<Lane::Range>& more) {
-        for (const auto& x : more) {
-            bool seen = false;
-            for (const auto& y : have) if (y.lo == x.lo && y.hi == x.hi) { seen = true; break; }
-            if (!seen) have.push_back(x);
-        }
-    };
-    // a lane this launch waits for: from here on this lane's order covers everything that lane has enqueued, so its ranges move
-    // here and it is no longer pending (a join need not wait for it, a later launch that touches those ranges follows THIS lane)
-    for (int k = 0; k < nh; k++) if (hazard[k] != li) {
-        Lane& H = c->lane[hazard[k]];
-        HIP_TRY(c, lane_mark(H));
-        HIP_TRY(c, hipStreamWaitEvent(L.own, H.done, 0));
-        add_new(L.reads, H.reads); add_new(L.writes, H.writes);
-        H.reads.clear(); H.writes.clear(); H.pending = false;
-    }
-    if (!nh) c->nextLane = (c->nextLane + 1) % c->nLanes;
-    add_new(L.reads, lc.rd);
-    add_new(L.writes, lc.wr);
+    lc.forked = true;
+    L.dirty = true;                                     // (the event itself: lane_mark, when somebody waits for the lane)
+    const uint32_t waits = c->book.commit(lc.pick, lc.ranges, lc.capNow, wait);
+    const hipError_t e = wait_for_lanes(c, L.own, waits);
+    if (e != hipSuccess) { c->book.keep_pending(waits, lc.capNow); return fail(c, EFFORT_ERR_HIP, "lane wait", e); }
     return EFFORT_OK;
 }
 
@@ -420,7 +345,7 @@ extern "C" int effort_set_overlap(effort_ctx* c, int lanes) {
             if (!L.done && !(L.done = pool_event(c->device))) return fail(c, EFFORT_ERR_HIP, "set_overlap: event");
         }
     }
-    c->nLanes = lanes; c->lastLane = 0; c->nextLane = 0;
+    c->book.reset(lanes); c->lastLane = 0;
     return EFFORT_OK;
 }
 extern "C" int effort_join(effort_ctx* c) {
@@ -460,7 +385,7 @@ extern "C" int effort_sync(effort_ctx* c) {
 // ---- weights ------------------------------------------------------------------------------------
 static int check_shape(uint32_t inDim, uint32_t outDim) {
     // bucketMul.swift:73 (outDim % 16), :52 tmpMulVec 16384 wide; probes need 4096 inputs (:36).  The reference also asserts
-    // (outDim/16) % 4 == 0 (:76: its kernel reads four columns per thread); this kernel masks a ragged last tile, so a
+    // (outDim/16) % 4 == 0 (:76: its kernel loads four columns per thread); this kernel masks a ragged last tile, so a
     // handle -- in particular a column shard of a multi-GPU split, 11008/16/8 = 86 columns -- may have any column count.
     // (an EVEN count: the row pieces are dword / dwordx2 loads, so rows must stay 4-byte aligned -- outDim % 32 == 0)
     if (inDim < (uint32_t)kProbes || outDim == 0 || outDim % 32 || outDim > 16384) return EFFORT_ERR_SHAPE;
@@ -546,7 +471,7 @@ extern "C" effort_w* effort_weights_q4(effort_ctx* c, const void* buckets, const
         bool ok = hipMalloc(&rowPtr, ((size_t)outDim + 2) * 4) == hipSuccess && hipMalloc(&w->olBlockPtr, ((size_t)olBlocks + 1) * 4) == hipSuccess &&
                   hipMalloc(&w->olMeta, (size_t)olBlocks * 64 * 4) == hipSuccess &&
                   hipMalloc(&w->olEntry, ((size_t)nOutliers + 64) * 4) == hipSuccess && hipMalloc(&tmp, 4 * (size_t)nOutliers * 4) == hipSuccess;
-        if (ok) ok = hipMemsetAsync(w->olEntry + (size_t)nOutliers, 0, 64 * 4, c->stream) == hipSuccess;     // padding: a step's load reads 64 entries from its cursor
+        if (ok) ok = hipMemsetAsync(w->olEntry + (size_t)nOutliers, 0, 64 * 4, c->stream) == hipSuccess;     // padding: a step's load takes 64 entries from its cursor
         if (ok) ok = launch_build_outlier_index(static_cast<const float*>(outliers), w->nOutliers, (uint32_t)inDim, (uint32_t)outDim, rowPtr, w->olBlockPtr,
                                                 w->olEntry, w->olMeta, tmp, c->stream) == hipSuccess;
         if (ok) ok = hipStreamSynchronize(c->stream) == hipSuccess;
@@ -581,7 +506,7 @@ extern "C" int effort_weights_refresh(effort_w* w) {
 // lines, the three column tiles of a row fetch 14 lines where 11 would do, and the stream runs at 5.4-5.6 TB/s instead of
 // the 6.1-6.9 TB/s it reaches on line-aligned rows (measured: 4096x11264 / 12288 / 8192).  This call gives the handle its
 // OWN copy of the buckets with every row starting on a 128-byte line (pitch = 2*cols rounded up to 128); the multiply
-// reads the copy, and the caller's buffer is no longer read (it may be freed; effort_weights_refresh re-reads it, so
+// streams the copy, and the caller's buffer is no longer read (it may be freed; effort_weights_refresh reads it again, so
 // keep it if the weights are going to change).  No-op when the pitch is line-aligned already.  Results are bit-identical.
 extern "C" int effort_weights_align_rows(effort_w* w) {
     if (!w || !w->ctx || w->dead) return EFFORT_ERR_ARG;
@@ -662,11 +587,11 @@ extern "C" effort_w* effort_weights_column_shard(const effort_w* full, int rank,
     *w = *full;
     w->view = true; w->parent = const_cast<effort_w*>(full); w->views = 0; w->dead = false;
     w->aligned = nullptr; w->rankBound = nullptr;
-    w->buckets = full->buckets + (size_t)rank * per;            // what the multiply reads (the full handle's own line-aligned copy, if it made one)
+    w->buckets = full->buckets + (size_t)rank * per;            // what the multiply streams (the full handle's own line-aligned copy, if it made one)
     w->viewTrim = (uint32_t)((size_t)rank * per * 2u);          // < rowPitch <= 2048: the descriptor stops where the full buffer does
     w->bucketsSrc = w->buckets; w->srcPitch = full->rowPitch;
     w->cols = per; w->outDim = outDim;
-    // the row means are row-global: the view reads the full handle's compact copy (means16 stays the parent's); the fixed-point bound is
+    // the row means are row-global: the view uses the full handle's compact copy (means16 stays the parent's); the fixed-point bound is
     // the FULL matrix's -- every rank rounds on the same grid -- in a word of the view's own (effort_weights_set_bound may change it)
     hipSetDevice(c->device);
     if (hipMalloc(&w->rankBound, (size_t)w->numExperts * 4) != hipSuccess ||
@@ -731,7 +656,7 @@ static int ensure_timing(effort_ctx* c) {
 // ---- launch planning: the inputs of plan_group (plan.hip) ------------------------------------------
 static PlanEnv plan_env(const effort_ctx* c, bool laned, bool thinEffort) {
     PlanEnv env;
-    env.numCU = c->numCU; env.nLanes = c->nLanes; env.laned = laned;
+    env.numCU = c->numCU; env.nLanes = c->book.nLanes; env.laned = laned;
     env.persistent = c->persistent; env.tuneW = c->tuneW; env.tuneE = c->tuneE; env.tuneS = c->tuneS;
     env.splitCutoff = c->splitCutoff; env.clock = c->clock;
     env.slabBytes = c->slabBytes; env.maxTiles = effort_ctx::kMaxTiles; env.maxSlices = effort_ctx::kMaxSlices;
@@ -782,17 +707,16 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
         pc[i] = plan_call(ws[i], pre, resids && resids[i]);
     }
     LaneChoice lc;
-    lc.laned = c->nLanes > 1 && !c->timing && !c->clock;
+    lc.laned = c->book.nLanes > 1 && !c->timing && !c->clock;
     const PlanEnv env = plan_env(c, lc.laned, thin_effort(n, efforts));
     GroupPlan plan;
     if (plan_group(fmt, env, n, pc, &plan) != EFFORT_OK) return fail(c, plan.err, plan.msg);
     const bool tm = c->timing && c->nSamples < effort_ctx::kMaxSamples;
     hipEvent_t* ev = tm ? c->ev + 4 * c->nSamples : nullptr;
     { const int lrc = choose_lane(c, lc, n, ws, vs, expNos, outs, vAux, resids); if (lrc != EFFORT_OK) return lrc; }
-    Lane& L = c->lane[lc.li];
+    Lane& L = c->lane[lc.pick.lane];
     const hipStream_t st = lc.laned ? L.own : c->stream;
-    LaneGuard guard{L};
-    c->lastLane = lc.li;
+    c->lastLane = lc.pick.lane;
     if (tm) HIP_TRY(c, hipEventRecord(ev[0], st));
     for (uint32_t l = 0; l < plan.nLaunches; l++) {    // (more than one: a group of more than kMaxGeoms shapes)
         const LaunchPlan& lp = plan.launch[l];
@@ -822,13 +746,13 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
             ga.wgEnd8[k] = (uint16_t)p.itemEnd8;
             L.lastSliceOff[i] = p.sliceOff; L.lastSlices[i] = p.g.slices;             // dispatch.size = sum of the per-slice counts
         }
-        { const int frc = fork_lane(c, lc, guard); if (frc != EFFORT_OK) return frc; }
+        { const int frc = fork_lane(c, lc); if (frc != EFFORT_OK) return frc; }
         if (c->splitCutoff && !(env.ablate & 1u)) HIP_TRY(c, launch_find_cutoff_group(ga, st));
         HIP_TRY(c, launch_bucket_mul(fmt, plan.W, plan.E, ga, st));
     }
     L.lastCalls = (uint32_t)n;
     if (tm) { HIP_TRY(c, hipEventRecord(ev[1], st)); c->nSamples++; }
-    return EFFORT_OK;                                  // (LaneGuard records the lane's `done` event)
+    return EFFORT_OK;
 }
 
 extern "C" int effort_bucketmul(effort_ctx* c, const effort_w* w, const float* v, const uint32_t* expNo, float* out, double effort) {
@@ -909,7 +833,7 @@ extern "C" int effort_debug_plan(int q4, int numCU, int lanes, int n, const int*
         !sliceRows || !launchOf || !launchPersistent || !launchCutJobs || !launchCompact || !launchStagger) return EFFORT_ERR_ARG;
     const Format fmt = q4 ? kQ4 : kFp16;
     effort_ctx c0;                                     // (a context's defaults; never created: no device behind it)
-    c0.numCU = numCU; c0.nLanes = lanes; c0.persistent = persistent; c0.tuneW = tuneW; c0.tuneE = tuneE; c0.tuneS = tuneS;
+    c0.numCU = numCU; c0.book.nLanes = lanes; c0.persistent = persistent; c0.tuneW = tuneW; c0.tuneE = tuneE; c0.tuneS = tuneS;
     c0.slabBytes = effort_ctx::kSlabBytes;
     PlanCall pc[kMaxGroup];
     for (int i = 0; i < n; i++) {
@@ -998,7 +922,7 @@ extern "C" int effort_convert_fp16_pitched(effort_ctx* c, const void* W, int out
         outDim % 16 || (outDim / 16) % 4)
         return fail(c, EFFORT_ERR_CONVERT, "convert_fp16: bucketize preconditions violated");
     const int pitch = rowPitchBytes ? rowPitchBytes : outDim / 16 * 2;
-    if (pitch < outDim / 16 * 2 || pitch % 8) return fail(c, EFFORT_ERR_CONVERT, "convert_fp16: row pitch must be a multiple of 8 bytes >= 2*cols");   // (the stats pass reads 8 bytes at a time)
+    if (pitch < outDim / 16 * 2 || pitch % 8) return fail(c, EFFORT_ERR_CONVERT, "convert_fp16: row pitch must be a multiple of 8 bytes >= 2*cols");   // (the stats pass loads 8 bytes at a time)
     const size_t elems = (size_t)outDim * inDim;
     if (elems > c->convElems) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1183,7 +1107,7 @@ extern "C" int effort_set_persistent(effort_ctx* c, int wgPerCU) {
 }
 
 extern "C" int effort_debug_hook_lane(effort_ctx* c, int lane) {
-    if (!c || lane < 0 || lane >= c->nLanes) return EFFORT_ERR_ARG;
+    if (!c || lane < 0 || lane >= c->book.nLanes) return EFFORT_ERR_ARG;
     c->lastLane = lane;
     return EFFORT_OK;
 }

@@ -218,6 +218,34 @@ def plan(calls, *, q4: bool = False, numCU: int = 256, lanes: int = 1, persisten
     return res
 
 
+def lanes(ops, *, lanes: int = 4) -> list[dict]:
+    """A script of operations through a fresh lane scheduler (effort_debug_lanes: csrc/lanes.hip without a context or a device; test /
+    tools hook).  ``ops``: ("launch", captureId, busy, reads, writes) -- reads / writes are lists of (lo, hi) address ranges --,
+    ("timed", captureId) for a launch in a timing mode, ("join", captureId).  Per operation a dict: ``rc``, ``joined_first`` (the book was
+    full), ``joined`` (lanes the context's stream waited for), ``lane``, ``fork_waited``, ``waits`` (lanes the launch's lane waited for) and
+    the state afterwards: ``pending``, ``nextLane``, ``busyStreak``, ``migrated``, ``reads`` / ``writes`` (ranges held, per lane)."""
+    kinds = {"launch": 0, "timed": 1, "join": 2}
+    words = []
+    for op in ops:
+        kind, cap, busy, rd, wr = tuple(op) + (0, (), ())[len(op) - 2:]
+        words += [kinds[kind], int(cap), int(bool(busy)), len(rd), len(wr)]
+        for lo, hi in list(rd) + list(wr):
+            words += [int(lo), int(hi)]
+    n, W = len(ops), 18
+    out = (C.c_int64 * max(n * W, 1))()
+    k = _lib.lib().effort_debug_lanes(lanes, n, (C.c_int64 * max(len(words), 1))(*words), len(words), out)
+    if k < 0:
+        raise _lib.EffortError(k, "lanes")
+    members = lambda mask: tuple(i for i in range(lanes) if mask >> i & 1)
+    res = []
+    for i in range(n):
+        r = out[i * W:(i + 1) * W]
+        res.append({"rc": r[0], "joined_first": bool(r[1]), "joined": members(r[2]), "lane": r[3], "fork_waited": bool(r[4]), "waits": members(r[5]),
+                    "pending": members(r[6]), "nextLane": r[7], "busyStreak": r[8], "migrated": bool(r[9]),
+                    "reads": list(r[10:10 + lanes]), "writes": list(r[14:14 + lanes])})
+    return res
+
+
 _gpus: dict[int, Gpu] = {}
 
 

@@ -61,6 +61,23 @@ EFFORT_API int effort_debug_plan(int q4, int numCU, int lanes, int n, const int*
                       const int* prologue, const int* hasResid, const double* effort, int persistent, int tuneW, int tuneE, int tuneS,
                       int* we, int* slices, int* tiles, int* sliceRows, int* launchOf,
                       int* launchPersistent, int* launchCutJobs, int* launchCompact, int* launchStagger);
+/* The lane scheduler on its own (csrc/lanes.hip: LaneBook, what effort_set_overlap's launches are ordered by): a script of nOps operations
+ * played through a fresh book of `lanes` lanes -- no context, no device, no HIP call.  `ops` is nWords int64 words, per operation
+ *   kind (EFFORT_LANES_*), capture id of the context's stream (0: not capturing), 1 if that stream answers "busy" / 0 if idle, nRead, nWrite,
+ *   then nRead and nWrite address ranges as (lo, hi) pairs -- what the launch reads and writes (a join or a timed launch: none).
+ * EFFORT_LANES_LAUNCH is a multiply launch, EFFORT_LANES_TIMED one in a timing / clock mode (the lanes are joined, lane 0), EFFORT_LANES_JOIN
+ * an effort_join.  `out` receives EFFORT_LANES_OUT_WORDS words per operation:
+ *   [0] the return code of the call; [1] 1 if the lanes were joined first because a lane's book was full; [2] the lanes the context's stream
+ *   waited for (a join, a timed launch, or [1]; sets of lanes are bit masks, bit i = lane i); [3] the launch's lane (-1: none); [4] 1 if the
+ *   lane's fork waited for the context's stream (busy, or capturing); [5] the lanes the launch's lane waited for;
+ *   the state afterwards: [6] the pending lanes, [7] the next round-robin lane, [8] the busy streak, [9] 1 if a chain moved since the last join,
+ *   [10..13] ranges read and [14..17] ranges written that each lane holds.
+ * Returns nOps, or EFFORT_ERR_ARG for a malformed script. */
+#define EFFORT_LANES_LAUNCH 0
+#define EFFORT_LANES_TIMED 1
+#define EFFORT_LANES_JOIN 2
+#define EFFORT_LANES_OUT_WORDS 18
+EFFORT_API int effort_debug_lanes(int lanes, int nOps, const int64_t* ops, int64_t nWords, int64_t* out);
 /* enable = 3 (device clock + trace): every work item of the most recent multiply launch leaves a 64-byte record
  * {item | workgroup << 32 (bit 63: cutoff job), XCC_ID | HW_ID << 32, six device wall-clock stamps: start, staged,
  * cutoff, selected, streamed, handed over}; copies the first maxRecords (<= 4096) records to host (8 u64 each), followed

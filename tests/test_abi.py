@@ -108,7 +108,7 @@ def test_shipped_library_reads_no_environment(hip_lib_built):
     for knob in (b"EFFORT_ABLATE", b"EFFORT_NO_CUTJOBS", b"EFFORT_NO_COMPACT_MEANS", b"EFFORT_TAIL_CALLS", b"EFFORT_TAIL_MULT"):
         assert knob not in blob, knob
     csrc = os.path.join(ROOT, "effort_amd", "csrc")
-    for obj in ("api.o", "bucket_mul.o", "cutoff.o", "dispatch.o", "decode.o", "gemv.o", "convert.o", "comm.o"):
+    for obj in ("api.o", "plan.o", "lanes.o", "bucket_mul.o", "cutoff.o", "dispatch.o", "decode.o", "gemv.o", "convert.o", "comm.o"):
         path = os.path.join(csrc, obj)
         if os.path.exists(path):
             syms = subprocess.run(["nm", "--undefined-only", path], capture_output=True, text=True, check=True).stdout

@@ -315,13 +315,14 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
 
 // Mixtral routing (runNetwork.swift:185-199): mpsTopK(topK: 2) of the gate logits, softmax over the two picked values.
 __device__ __forceinline__ void top2_softmax_scan(const float* gate, uint32_t n, uint32_t* __restrict__ idx, float* __restrict__ val) {
-    uint32_t i0 = 0, i1 = 0xFFFFFFFFu; float v0 = -INFINITY, v1 = -INFINITY;
+    uint32_t i0 = 0xFFFFFFFFu, i1 = 0xFFFFFFFFu; float v0 = -INFINITY, v1 = -INFINITY;
     for (uint32_t i = 0; i < n; i++) {
         const float x = gate[i];
-        if (x > v0) { v1 = v0; i1 = i0; v0 = x; i0 = i; }
+        if (x > v0) { v1 = v0; i1 = i0; v0 = x; i0 = i; }     // (the first hit hands on i0's "none yet", not an index)
         else if (x > v1) { v1 = x; i1 = i; }
     }
-    if (i1 == 0xFFFFFFFFu) { i1 = i0; v1 = v0; }
+    if (i0 == 0xFFFFFFFFu) i0 = 0;                            // nothing above -inf: a valid index all the same
+    if (i1 == 0xFFFFFFFFu) { i1 = i0; v1 = v0; }              // no runner-up (one expert): the winner twice, 0.5 / 0.5
     const float e1 = expf(v1 - v0), inv = 1.0f / (1.0f + e1);
     idx[0] = i0; idx[1] = i1; val[0] = inv; val[1] = e1 * inv;
 }

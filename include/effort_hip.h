@@ -312,7 +312,7 @@ EFFORT_API int effort_top2_softmax(effort_ctx* ctx, const float* gate_dev, int n
 EFFORT_API int effort_mix2(effort_ctx* ctx, const float* f0_dev, const float* f1_dev, const float* val2_dev, float* out_dev, int n);
 /* Mixtral routing in ONE launch (runNetwork.swift:173-175,185-189): x = h / sqrt(mean(h^2) + 1e-5) * norm_w; gate[e] = sum f16(x) * gate[e][.]
  * (exact f16 products, f32 sums; gate f16 [numExperts][n]); idx2_dev = the two largest logits' experts (strict >, lowest index first; with
- * numExperts == 1 expert 0 is picked twice with the weights 1.0 / 0.0, as effort_top2_softmax writes them), val2_dev = softmax over
+ * numExperts == 1 expert 0 is picked twice with the weights 0.5 / 0.5, as effort_top2_softmax writes them), val2_dev = softmax over
  * those two.  Bit for bit what effort_add_rmsnorm_mul(h, NULL, norm_w, x) ->
  * effort_dense_gemv(gate, x, logits) on the in-tree kernel -> effort_top2_softmax write in a row; h is not modified.  gate_out_dev
  * (may be NULL) receives the numExperts logits, for tests and debugging.  n % 16 == 0, 16 <= n <= 16384, 1 <= numExperts <= 64;

@@ -64,8 +64,8 @@ def _route(ea, h, w, gate, with_logits=True):
 @pytest.mark.parametrize("n,numExperts", [(4096, 8), (4112, 4), (1024, 2), (2048, 20), (512, 1)])
 def test_route_equals_the_three_call_chain(ea, n, numExperts):
     """gate_out, idx2 and val2 bit for bit against the chain.  With ONE expert the chain picks expert 0 twice with the weights
-    1.0 / 0.0 -- top2_softmax_kernel's scan leaves the runner-up at -inf there, its `picked twice` fallback is never reached -- not
-    0.5 / 0.5; the mix of one expert with itself is the same either way, and the route reproduces what the chain writes."""
+    0.5 / 0.5 (the softmax of a logit with itself; tests/test_gpu_glue.py pins top2_softmax to that), and the route reproduces what
+    the chain writes."""
     h, w, gate = _route_inputs(n, numExperts, seed=n + numExperts)
     _, want_logits, want_idx, want_val = _chain(ea, h, w, gate)
     logits, idx, val = _route(ea, h, w, gate)

@@ -331,6 +331,78 @@ def test_dense_gemv_matches_oracle(ea, oracle_cpu, outDim, inDim):
         assert np.allclose(out.cpu().numpy(), want, rtol=tol, atol=tol * np.abs(want).max()), rocblas
 
 
+# The kernel's other instantiations and branches (csrc/gemv.hip), against the float64 reference of tests/glue_reference.py in the band
+# of the test above:
+#   (8193, 512)    <ROWS 2, AUX 0> (outDim > 8192), an odd last row without a partner
+#   (8200, 4096)   <2, 2>: 67.2 MB, above kGemvKeepBytes -- the non-temporal weight stream
+#   (8192, 4112)   <1, 2>, a ragged last 512-element chunk
+#   (24, 24592)    the first inDim whose f16 staging of v passes 48 KB of LDS (allow_full_lds)
+#   (16, 65536)    the largest inDim the kernel serves: 128 KB of LDS
+DENSE_F64_SHAPES = [(8193, 512), (8200, 4096), (8192, 4112), (24, 24592), (16, 65536)]
+DENSE_BAND = 1e-5
+
+
+def dense_close(out, want, tol=DENSE_BAND):
+    return bool(np.allclose(out, want, rtol=tol, atol=tol * np.abs(want).max()))
+
+
+@pytest.mark.parametrize("outDim,inDim", DENSE_F64_SHAPES)
+def test_dense_gemv_instantiations_match_float64(ea, outDim, inDim):
+    from tests import glue_reference
+    W = make_w(outDim, inDim, seed=3)
+    v = make_v(inDim, seed=9, heavy=True)
+    want = glue_reference.dense(W, v)
+    g = ea.gpu()
+    Wd, vd = dev16(W).view(torch.float16), devf(v)
+    nontemporal = outDim * inDim * 2 > 64 << 20                       # rocBLAS adds nothing at the two 67 MB shapes
+    for rocblas in (False,) if nontemporal else (False, True):
+        out = torch.full((outDim + 8,), float("nan"), device=DEV)
+        out[outDim:] = -555.0
+        try:
+            g.set_dense_backend(rocblas)
+            ea.basicMul(vd, Wd, out[:outDim])
+            g.eval()
+        finally:
+            g.set_dense_backend(False)
+        got = out.cpu().numpy()
+        assert (got[outDim:] == -555.0).all(), rocblas
+        assert dense_close(got[:outDim], want, 1e-3 if rocblas else DENSE_BAND), (rocblas, float(np.abs(got[:outDim] - want).max() / np.abs(want).max()))
+
+
+def test_dense_gemv_unaligned_input_is_bit_equal(ea):
+    """v at a 4-byte but not 16-byte aligned address takes the scalar staging branch: the same f16(v) in LDS, hence the same bits out."""
+    from tests import glue_reference
+    outDim, inDim = 1027, 4112
+    W = make_w(outDim, inDim, seed=3)
+    v = make_v(inDim, seed=9, heavy=True)
+    g = ea.gpu()
+    g.set_dense_backend(False)
+    Wd = dev16(W).view(torch.float16)
+    aligned, shifted = devf(v), devf(np.concatenate([np.zeros(1, np.float32), v]))[1:]
+    assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4
+    outs = [torch.full((outDim,), float("nan"), device=DEV) for _ in range(2)]
+    ea.basicMul(aligned, Wd, outs[0])
+    ea.basicMul(shifted, Wd, outs[1])
+    g.eval()
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
+    assert dense_close(outs[1].cpu().numpy(), glue_reference.dense(W, v))
+
+
+def test_dense_gemv_expert_matches_float64(ea):
+    """effort_dense_gemv_expert at (8193, 512), 3 experts: experts 0 and 2, and the device value 7 clamped to the last expert."""
+    from tests import glue_reference
+    outDim, inDim = 8193, 512
+    Ws = [make_w(outDim, inDim, seed=3 + e) for e in range(3)]
+    v = make_v(inDim, seed=9, heavy=True)
+    cores = dev16(np.stack(Ws)).view(torch.float16)
+    vd = devf(v)
+    for expNo in (0, 2, 7):
+        out = torch.full((outDim,), float("nan"), device=DEV)
+        ea.basicMulExpert(vd, cores, torch.tensor([expNo], dtype=torch.int32, device=DEV), out)
+        ea.gpu().eval()
+        assert dense_close(out.cpu().numpy(), glue_reference.dense(Ws[min(expNo, 2)], v)), expNo
+
+
 def test_error_reporting(ea, oracle_cpu):
     import effort_amd
     W, b, s, p = converted(oracle_cpu, 256, 4096)

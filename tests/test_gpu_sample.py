@@ -147,6 +147,7 @@ def test_greedy_settings_equal_argmax(gpu, rows, family):
             if hl == 4 and n not in (5, 1025, 32000):
                 continue
             want = pick(gpu, x, n, None, pos0, hl)
+            assert want[0] == next(iter(topk_reference(make(family, n), 1)[0].tolist()), 0), (family, n)    # the host answer; every logit NaN: token 0
             assert want[2] == pos0 + 1 and want[3] == (2 if np.isnan(make(family, n)).all() else 0) | (1 if pos0 >= hl else 0)
             for s in (Sampling(top_k=1, temperature=0.8, seed=n), Sampling(top_k=40, temperature=0.0, seed=n),
                       Sampling(top_k=40, temperature=float("nan")), Sampling(top_k=64, temperature=float("inf"), top_p=0.5)):

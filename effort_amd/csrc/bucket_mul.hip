@@ -798,9 +798,14 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     // read-add-write needs a PRIVATE tile per wave (W x the LDS, so two workgroups per CU at best) and two LDS
     // instructions per element; ds_add_f32 runs at 0.5 elements/clk/CU; ds_add_u32 runs at 13 (tools/lab/microbench.hip),
     // lets all waves share one tile, and -- integer addition being associative -- makes the sum independent of the
-    // order in which waves and workgroups happen to run.  Each product is rounded once to the grid 2^-k (k above: at
-    // least 30 bits below the bound L), finer than the f32 rounding of a running sum; the reference's own summation
-    // order is unspecified (atomics / simd_sum), see DESIGN.md.
+    // order in which waves and workgroups happen to run.  Each product is rounded once to the grid 2^-k (k above: the
+    // step lies in (L * 2^-30, L * 2^-29], L the bound of THIS slice), so an output of m products is off by about
+    // sqrt(m / 12) * L * 2^-29.5.  That is finer than the f32 rounding of a running sum (steps of 2^-24 |out|) only while
+    // L / max|out| of the slice stays below about 2^5: i.i.d. Gaussian weights at one scale have 2^9 on the whole input,
+    // 2^4 on one of 32 slices.  A per-channel scale spread, a large input channel or one large weight raise the bound and
+    // not the outputs (2^11 .. 2^18 measured): the error then exceeds an f32 sum's, and 2e-5 of max|out| once the slice's
+    // ratio passes about 2^8 (DESIGN.md 2.1 has the measured table).  The reference's own summation order is unspecified
+    // (atomics / simd_sum), see DESIGN.md.
     // The LDS byte address is built with v_bfe_u32 + v_lshl_add_u32 (hipcc otherwise spends three VALU ops on it).
     using lds_i = __attribute__((address_space(3))) int;
     const uint32_t accB = (uint32_t)(size_t)(lds_i*)(acc + lane);

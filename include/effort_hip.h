@@ -140,8 +140,16 @@ EFFORT_API void effort_weights_free(effort_w* w);
 /* The multiply accumulates in fixed point; its scale comes from a per-expert bound on the weights (sum over ranks of the
  * rank's largest |w|; Q4: largest row mean) read at registration.  If the borrowed buffers are REWRITTEN afterwards (the
  * reference's loader.swift buffers are mutable) call effort_weights_refresh before the next multiply: with a stale bound
- * the sums of larger weights wrap.  get/set copy the bound ([numExperts] floats, host memory): a column shard of a
- * multi-GPU split can take the full matrix's bound, so that every rank rounds its products on the same grid.
+ * the sums of larger weights can wrap (a bound too SMALL by a factor g wraps an output that exceeds 2/g of the true bound L
+ * below; short of that it merely makes the grid finer; one that is too LARGE makes it coarser in proportion).  get/set copy the bound
+ * ([numExperts] floats, host memory): a column shard of a multi-GPU split can take the full matrix's bound, so that every
+ * rank rounds its products on the same grid.
+ * What the bound costs: a workgroup rounds each product to a step in (L * 2^-30, L * 2^-29], L = (sum of |v_j| over its row
+ * slice) * bound, so an output of m products is off by about sqrt(m / 12) * L * 2^-29.5.  Against max|out| that is 1-6e-6 for
+ * weights at ONE scale (L / max|out| about 2^9 on the whole input, divided by the slice count) and finer than an f32 running
+ * sum while the slice's L / max|out| stays below about 2^5.  The bound is a worst case over every input channel: a per-channel
+ * scale spread, one large channel or one large weight raise L and not the outputs (L / max|out| 2^11 .. 2^18 measured), and the
+ * error grows in proportion -- past 2e-5 * max|out| once the slice's ratio exceeds about 2^8 (measured table).
  * FP16 handles also keep a compact copy of the row means (stats lane .w, 2 bytes per bucket row: +0.15 % of the buckets'
  * size) that big launches stage instead of the 8-byte stats; effort_weights_refresh re-reads it with the bound. */
 EFFORT_API int effort_weights_refresh(effort_w* w);
@@ -165,7 +173,8 @@ EFFORT_API int effort_weights_set_bound(effort_w* w, const float* host_in);
  * expNo_dev = device u32 expert index (NULL = expert 0; expertMul.swift:18-22), effort in [0,1].
  * Row selection (cutoff, dispatch set) is bit-exact with the reference's arithmetic.  Products are accumulated in
  * per-workgroup fixed point: order-free, hence bit-identical run to run; within 2e-5 * max|out| of
- * an f32 accumulation (measured 1-4e-6). */
+ * an f32 accumulation for weights at one scale (measured 1-6e-6), beyond it where the weights' bound is loose (see
+ * effort_weights_refresh above and DESIGN.md 2.1). */
 EFFORT_API int effort_bucketmul(effort_ctx* ctx, const effort_w* w, const float* v_dev, const uint32_t* expNo_dev,
                      float* out_dev, double effort);
 

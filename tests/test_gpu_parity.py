@@ -107,6 +107,8 @@ def test_cutoff_across_input_scales(ea, oracle_cpu):
                 ea.bucketMul(vd, ew, None, out, effort)
                 ea.gpu().eval()
                 assert np.float32(ea.gpu().last_cutoff()).tobytes() == np.float32(cutoff).tobytes(), (k, mult, effort)
+                want, n, _ = oracle_cpu.bucket_mul(v, b, s, p, inDim, outDim, effort)
+                assert ea.gpu().last_dispatch_count() == n and close(out.cpu().numpy(), want), (k, mult, effort)
                 seen_small += cutoff < 128.0
                 seen_big += cutoff >= 128.0
     assert seen_small > 10 and seen_big > 10, (seen_small, seen_big)
@@ -196,9 +198,10 @@ def test_launch_geometries_agree_and_are_deterministic(ea, oracle_cpu, waves, el
 
 def test_experts_and_percentload(ea, oracle_cpu):
     """expNo offsets into a stacked buffer (bucketMul.metal:58) and percentLoad truncates the rank planes
-    (loader.swift:157-159)."""
+    (loader.swift:157-159).  The three experts differ in scale by 64 either way: each is summed on the fixed-point grid of its OWN
+    bound (expert 0's grid is 64 times too coarse for expert 1)."""
     outDim, inDim = 256, 4096
-    mats = [converted(oracle_cpu, outDim, inDim, seed=100 + e) for e in range(3)]
+    mats = [converted(oracle_cpu, outDim, inDim, seed=100 + e, scale=0.02 * m) for e, m in enumerate((1.0, 1.0 / 64.0, 64.0))]
     ews = [gpu_weights(ea, *m) for m in mats]
     stacked = ea.ExpertWeights.stack(ews)
     B = np.concatenate([m[1] for m in mats])

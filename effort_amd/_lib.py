@@ -107,6 +107,8 @@ _SIGS = {
     "effort_debug_stamps": (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
     "effort_debug_slice_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.c_int]),
     "effort_debug_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "effort_debug_variants": (C.c_int, [C.c_int, _P, C.c_int]),
+    "effort_debug_last_variant": (C.c_int, [_P, C.c_int, _P]),
     "effort_debug_lanes": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),
     "effort_debug_trace": (C.c_int, [_P, C.POINTER(C.c_ulonglong), C.c_int]),
     "effort_kernel_clock": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

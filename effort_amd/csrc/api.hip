@@ -38,6 +38,9 @@ struct Lane {
     uint32_t* d_queue = nullptr;      // item queues of persistent launches
     // where each call of the lane's last (group) launch keeps its per-slice counts; slices == 0: dispatch.size is d_count
     uint32_t lastCalls = 1, lastSliceOff[effort::kMaxGroup] = {0}, lastSlices[effort::kMaxGroup] = {0};
+    // what each launch of the lane's last group ran (launch_mul_t fills it; effort_debug_last_variant)
+    uint32_t lastLaunches = 0;
+    effort::LaunchedVariant lastVariant[effort::kMaxLaunches] = {};
 };
 
 struct effort_ctx {
@@ -718,6 +721,7 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
     const hipStream_t st = lc.laned ? L.own : c->stream;
     c->lastLane = lc.pick.lane;
     if (tm) HIP_TRY(c, hipEventRecord(ev[0], st));
+    L.lastLaunches = 0;
     for (uint32_t l = 0; l < plan.nLaunches; l++) {    // (more than one: a group of more than kMaxGeoms shapes)
         const LaunchPlan& lp = plan.launch[l];
         GroupKArgs ga;
@@ -748,7 +752,8 @@ static int do_group(effort_ctx* c, Format fmt, int n, const effort_w* const* ws,
         }
         { const int frc = fork_lane(c, lc); if (frc != EFFORT_OK) return frc; }
         if (c->splitCutoff && !(env.ablate & 1u)) HIP_TRY(c, launch_find_cutoff_group(ga, st));
-        HIP_TRY(c, launch_bucket_mul(fmt, plan.W, plan.E, ga, st));
+        HIP_TRY(c, launch_bucket_mul(fmt, plan.W, plan.E, ga, st, &L.lastVariant[l]));
+        L.lastLaunches = l + 1u;
     }
     L.lastCalls = (uint32_t)n;
     if (tm) { HIP_TRY(c, hipEventRecord(ev[1], st)); c->nSamples++; }
@@ -795,6 +800,7 @@ extern "C" int effort_calc_dispatch(effort_ctx* c, const effort_w* w, const floa
     HIP_TRY(c, launch_find_cutoff(v, w->probes, expNo, q, L.d_cutoff, L.d_count, nullptr, c->stream));
     HIP_TRY(c, launch_calc_dispatch(w->fmt, w->stats, v, expNo, L.d_cutoff, g, dispatch, count, L.d_count, c->d_blockScratch, c->stream));
     L.lastCalls = 1; L.lastSlices[0] = 0;        // dispatch.size is the scalar written by the scan kernel
+    L.lastLaunches = 0;                          // (no multiply kernel ran)
     return EFFORT_OK;
 }
 
@@ -856,6 +862,21 @@ extern "C" int effort_debug_plan(int q4, int numCU, int lanes, int n, const int*
         launchPersistent[l] = (int)lp.persistent; launchCutJobs[l] = (int)lp.cutJobs; launchCompact[l] = lp.compact ? 1 : 0; launchStagger[l] = (int)lp.staggerSleeps;
     }
     return (int)plan.nLaunches;
+}
+// The instantiations that exist, without a context or a device (include/effort_hip_debug.h).
+extern "C" int effort_debug_variants(int q4, int* rows, int maxRows) {
+    if (maxRows < 0 || (maxRows > 0 && !rows)) return EFFORT_ERR_ARG;
+    return bucket_mul_variants(q4 ? kQ4 : kFp16, rows, maxRows);
+}
+// What launch `launch` of the most recent group ran: host-side record, nothing is read from the device.
+extern "C" int effort_debug_last_variant(effort_ctx* c, int launch, int* out8) {
+    if (!c || !out8 || launch < 0) return EFFORT_ERR_ARG;
+    const Lane& L = c->lane[c->lastLane];
+    if ((uint32_t)launch >= L.lastLaunches) return EFFORT_ERR_ARG;
+    const LaunchedVariant& v = L.lastVariant[launch];
+    const uint32_t w[8] = {v.W, v.E, v.fused, v.compact, v.lean, v.persistent, v.grid, v.totalItems};
+    for (int i = 0; i < 8; i++) out8[i] = (int)w[i];
+    return EFFORT_OK;
 }
 extern "C" int effort_group_cutoff(effort_ctx* c, int idx, float* host_out) {
     if (!c || !host_out || idx < 0 || (uint32_t)idx >= c->lane[c->lastLane].lastCalls) return EFFORT_ERR_ARG;

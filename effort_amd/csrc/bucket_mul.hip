@@ -1455,7 +1455,7 @@ static hipError_t each_variant(F&& f) {
 }
 
 template <int FMT, int E, int W>
-static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
+static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st, LaunchedVariant* ran) {
     GroupKArgs ga = gaIn;
     // plain grids of the product path (no stamps, no ablation switches) run the lean instantiation
     constexpr bool kLean = W == 8;
@@ -1493,6 +1493,7 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st) {
     const hipError_t err = each_variant<FMT, E, W>([&](auto kernel, bool fu, bool co, bool pe) -> hipError_t {
         if (launched || fu != fusedAny || co != compact || pe == lean) return hipSuccess;
         launched = true;
+        if (ran) *ran = LaunchedVariant{(uint32_t)W, (uint32_t)E, fu, co, !pe, ga.persistent, grid, ga.totalItems};      // (host only: effort_debug_last_variant)
         hipLaunchKernelGGL(kernel, gd, bd, lds, st, ga);
         return hipGetLastError();
     });
@@ -1529,10 +1530,28 @@ static bool with_geom(int W, int E, F&& f) {
     return false;
 }
 
-hipError_t launch_bucket_mul(Format fmt, int W, int E, const GroupKArgs& a, hipStream_t st) {
+hipError_t launch_bucket_mul(Format fmt, int W, int E, const GroupKArgs& a, hipStream_t st, LaunchedVariant* ran) {
     hipError_t err = hipErrorInvalidValue;
-    with_geom(W, E, [&](auto w, auto e) { err = fmt == kFp16 ? launch_mul_t<kFp16, decltype(e)::value, decltype(w)::value>(a, st) : launch_mul_t<kQ4, decltype(e)::value, decltype(w)::value>(a, st); });
+    with_geom(W, E, [&](auto w, auto e) { err = fmt == kFp16 ? launch_mul_t<kFp16, decltype(e)::value, decltype(w)::value>(a, st, ran) : launch_mul_t<kQ4, decltype(e)::value, decltype(w)::value>(a, st, ran); });
     return err;
+}
+
+// The instantiations that exist for a format, as rows {W, E, fused, compact, lean}: EFFORT_GEOMS x each_variant, the walk of
+// bucket_mul_prepare_device and of the launch selection (host only, no HIP call: effort_debug_variants).  Returns their number; fills
+// at most maxRows rows.
+int bucket_mul_variants(Format fmt, int* rows, int maxRows) {
+    int n = 0;
+    auto note = [&](int w, int e) {
+        return [&n, rows, maxRows, w, e](auto, bool fu, bool co, bool pe) -> hipError_t {
+            if (rows && n < maxRows) { int* r = rows + 5 * n; r[0] = w; r[1] = e; r[2] = fu; r[3] = co; r[4] = !pe; }
+            n++;
+            return hipSuccess;
+        };
+    };
+#define EFFORT_CASE(w, e) if (fmt == kFp16) each_variant<kFp16, e, w>(note(w, e)); else each_variant<kQ4, e, w>(note(w, e));
+    EFFORT_GEOMS(EFFORT_CASE)
+#undef EFFORT_CASE
+    return n;
 }
 
 size_t bucket_mul_lds_bytes(Format fmt, int W, int E, const MulGeom& g, bool lean) {

@@ -212,8 +212,11 @@ hipError_t launch_dense_gemv_expert(const uint16_t* W_f16, const uint32_t* expNo
 hipError_t launch_find_cutoff(const float* v, const uint16_t* probes, const uint32_t* expNo, uint32_t q,
                               float* cutoff, uint32_t* dispatchCount, unsigned long long* tstamp, hipStream_t st);
 
-// Returns hipErrorInvalidValue for unsupported (fmt, W, E).
-hipError_t launch_bucket_mul(Format fmt, int wavesPerGroup, int elemsPerLane, const GroupKArgs& ga, hipStream_t st);
+// What a multiply launch ran: the instantiation launch_mul_t chose and its grid (host only: effort_debug_last_variant).
+struct LaunchedVariant { uint32_t W, E, fused, compact, lean, persistent, grid, totalItems; };
+// Returns hipErrorInvalidValue for unsupported (fmt, W, E).  `ran` (nullable): filled where the kernel is launched.
+hipError_t launch_bucket_mul(Format fmt, int wavesPerGroup, int elemsPerLane, const GroupKArgs& ga, hipStream_t st, LaunchedVariant* ran = nullptr);
+int bucket_mul_variants(Format fmt, int* rows, int maxRows);      // rows of {W, E, fused, compact, lean}: the instantiations that exist; returns their number
 hipError_t bucket_mul_prepare_device();     // once per device: the kernels may use the whole LDS (hipFuncSetAttribute)
 hipError_t launch_find_cutoff_group(const GroupKArgs& ga, hipStream_t st);    // ga.cutoff[i] of every call
 size_t bucket_mul_lds_bytes(Format fmt, int wavesPerGroup, int elemsPerLane, const MulGeom& g, bool lean);    // lean: with the lean Q4 kernels' region for v (plan_lds)

@@ -186,6 +186,13 @@ class Gpu:
         self.check(self._lib.effort_group_cutoff(self.ctx, int(idx), C.byref(x)), "last_cutoff")
         return float(x.value)
 
+    def last_variant(self, launch: int = 0) -> dict:
+        """What launch ``launch`` of the most recent multiply group ran (effort_debug_last_variant; host-side record, test hook): ``variant`` =
+        (W, E, fused, compact, lean), ``persistent`` (workgroups per CU; 0: a plain grid), ``grid`` (workgroups) and ``totalItems``."""
+        buf = (C.c_int * 8)()
+        self.check(self._lib.effort_debug_last_variant(self.ctx, int(launch), buf), "last_variant")
+        return {"variant": (buf[0], buf[1], bool(buf[2]), bool(buf[3]), bool(buf[4])), "persistent": buf[5], "grid": buf[6], "totalItems": buf[7]}
+
     def close(self):
         if getattr(self, "ctx", None):
             self._lib.effort_destroy(self.ctx)
@@ -216,6 +223,19 @@ def plan(calls, *, q4: bool = False, numCU: int = 256, lanes: int = 1, persisten
     res.update({name: list(a[:n]) for name, a in zip(("slices", "tiles", "sliceRows", "launch"), per_call)})
     res.update({name: list(a[:k]) for name, a in zip(("persistent", "cutJobs", "compact", "stagger"), per_launch)})
     return res
+
+
+def variants(q4: bool = False) -> list[tuple]:
+    """The instantiations of the multiply kernel that exist for a format, as (W, E, fused, compact, lean) in the order the library walks
+    them (effort_debug_variants: no context, no device; test hook)."""
+    n = _lib.lib().effort_debug_variants(int(q4), None, 0)
+    if n < 0:
+        raise _lib.EffortError(n, "variants")
+    buf = (C.c_int * (5 * n))()
+    k = _lib.lib().effort_debug_variants(int(q4), buf, n)
+    if k != n:
+        raise _lib.EffortError(min(k, -1), "variants")
+    return [(buf[5 * i], buf[5 * i + 1], bool(buf[5 * i + 2]), bool(buf[5 * i + 3]), bool(buf[5 * i + 4])) for i in range(n)]
 
 
 def lanes(ops, *, lanes: int = 4) -> list[dict]:

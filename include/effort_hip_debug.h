@@ -61,6 +61,15 @@ EFFORT_API int effort_debug_plan(int q4, int numCU, int lanes, int n, const int*
                       const int* prologue, const int* hasResid, const double* effort, int persistent, int tuneW, int tuneE, int tuneS,
                       int* we, int* slices, int* tiles, int* sliceRows, int* launchOf,
                       int* launchPersistent, int* launchCutJobs, int* launchCompact, int* launchStagger);
+/* The instantiations of the multiply kernel that exist for a format (q4 = 0: FP16), as rows of five ints {waves per workgroup, columns per
+ * lane, fused (prologue / residual), compact (FP16: compact row means), lean (the plain-grid instantiation)}: the list the device preparation
+ * and the launch selection walk (bucket_mul.hip: EFFORT_GEOMS x each_variant).  No context, no device, no HIP call.  Fills at most maxRows rows
+ * (rows may be NULL with maxRows = 0) and returns the number that exist. */
+EFFORT_API int effort_debug_variants(int q4, int* rows, int maxRows);
+/* What launch `launch` (0 .. launches - 1; a group splits when it holds more than four shapes) of the most recent multiply group of the hooked
+ * lane ran, as the launcher recorded it on the host: out8 = {waves, columns per lane, fused, compact, lean, persistent workgroups per CU (0: a
+ * plain grid), grid size in workgroups, items of the launch (without cutoff jobs)}.  EFFORT_ERR_ARG when the group had no such launch. */
+EFFORT_API int effort_debug_last_variant(effort_ctx* ctx, int launch, int* out8);
 /* The lane scheduler on its own (csrc/lanes.hip: LaneBook, what effort_set_overlap's launches are ordered by): a script of nOps operations
  * played through a fresh book of `lanes` lanes -- no context, no device, no HIP call.  `ops` is nWords int64 words, per operation
  *   kind (EFFORT_LANES_*), capture id of the context's stream (0: not capturing), 1 if that stream answers "busy" / 0 if idle, nRead, nWrite,

@@ -96,6 +96,8 @@ def test_null_arguments_are_reported_not_crashed(hip_lib_built):
     assert lib.effort_sync(None) == -1
     assert lib.effort_bucketmul(None, None, None, None, None, 0.25) == -1
     assert lib.effort_set_tuning(None, 0, 0, 0) == -1
+    assert lib.effort_debug_last_variant(None, 0, None) == -1
+    assert lib.effort_debug_variants(0, None, 1) == -1                # rows asked for, nowhere to put them
     assert lib.effort_last_error(None) == b"null context"
 
 
@@ -232,6 +234,15 @@ def test_shipped_kernels_keep_their_register_budget(hip_lib_built, tmp_path):
         assert int(r[".private_segment_fixed_size"]) == 0, (sym, r[".private_segment_fixed_size"])
         assert int(r[".vgpr_count"]) <= 128, (sym, r[".vgpr_count"])
     assert wide == 33, wide
+    # ... and they are the rows effort_debug_variants reports, format by format: <FMT, E, W, FUSED, COMPACT, PERSIST> of each symbol as (W, E, fused, compact, lean)
+    from effort_amd import runtime
+    built = {0: set(), 1: set()}
+    for sym in res:
+        fmt, E, W, fu, co, pe = (int(x) for x in re.search(r"bucket_mul_kernelILi(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)E", sym).groups())
+        built[fmt].add((W, E, bool(fu), bool(co), not pe))
+    for q4 in (0, 1):
+        rows = runtime.variants(bool(q4))
+        assert len(rows) == len(set(rows)) and set(rows) == built[q4], (q4, set(rows) ^ built[q4])
 
 
 def test_shipped_library_has_no_measured_dead_ends(hip_lib_built):

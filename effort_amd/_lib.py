@@ -107,6 +107,7 @@ _SIGS = {
     "effort_debug_stamps": (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
     "effort_debug_slice_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.c_int]),
     "effort_debug_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "effort_debug_check_bundle": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "effort_debug_variants": (C.c_int, [C.c_int, _P, C.c_int]),
     "effort_debug_last_variant": (C.c_int, [_P, C.c_int, _P]),
     "effort_debug_lanes": (C.c_int, [C.c_int, C.c_int, _P, C.c_int64, _P]),

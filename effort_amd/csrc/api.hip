@@ -394,6 +394,37 @@ static int check_shape(uint32_t inDim, uint32_t outDim) {
     if (inDim < (uint32_t)kProbes || outDim == 0 || outDim % 32 || outDim > 16384) return EFFORT_ERR_SHAPE;
     return EFFORT_OK;
 }
+// What a bundle's sizes must satisfy beyond check_shape, for both formats (Q4: percentLoad 8, rows 2 * outDim/32 bytes apart).  The multiply
+// addresses EVERY per-row array through 32-bit buffer descriptors and 32-bit byte offsets, so each array of the whole stack must end below
+// 4 GiB: with rows = numExperts * percentLoad * inDim,
+//   the buckets      rows * pitch   (mul_item: boff = (vRow0 + rowIdx) * vRowPitch, the descriptor's vRecords; effort_weights_align_rows asks again for its pitch),
+//   the stats        rows * 8       (stage_issue: make_rsrc(a.stats, ...), voff = (rowBase + ...) * 8 + 4; Q4: ((rowBase + ...) * 2 + 1) * 4) -- the
+//                                   larger of the two where a bucket row is shorter than 8 bytes (FP16 outDim 32; Q4 outDim 32, 64, 96),
+//   the compact means rows * 2      (FP16: a quarter of the stats, covered by them).
+// Every other 32-bit product over rows is a ROW NUMBER or an element count and smaller than these: rowBase = e * expertRows and
+// vRow0 = e * expertRows + j0 (* 8) are below rows <= 2^29; launch_rank_bound / launch_compact_means take rows itself; calc_dispatch's
+// i * g.cols (dispatch.hip) is below rows * cols = half the buckets' bytes at most.  (All for e < numExperts: the caller's contract.)
+// Returns the row pitch through *pitchOut.
+static int check_bundle(Format fmt, int inDim, int outDim, int percentLoad, int numExperts, int rowPitchBytes, uint32_t* pitchOut) {
+    if (inDim <= 0 || outDim <= 0 || numExperts < 1 || inDim > 65535 || check_shape((uint32_t)inDim, (uint32_t)outDim) != EFFORT_OK) return EFFORT_ERR_SHAPE;
+    int pitch;
+    if (fmt == kFp16) {
+        if (percentLoad < 1 || percentLoad > 16) return EFFORT_ERR_SHAPE;
+        pitch = rowPitchBytes ? rowPitchBytes : outDim / 16 * 2;
+        if (pitch < outDim / 16 * 2 || pitch % 4) return EFFORT_ERR_SHAPE;
+    } else {
+        if (rowPitchBytes) return EFFORT_ERR_SHAPE;
+        percentLoad = 8; pitch = outDim / 32 * 2;
+    }
+    const size_t rows = (size_t)numExperts * (size_t)percentLoad * (size_t)inDim;
+    if (rows * (size_t)pitch > 0xFFFFFFFFull || rows * 8u > 0xFFFFFFFFull) return EFFORT_ERR_SHAPE;
+    if (pitchOut) *pitchOut = (uint32_t)pitch;
+    return EFFORT_OK;
+}
+// check_bundle without a context or a device (include/effort_hip_debug.h).
+extern "C" int effort_debug_check_bundle(int q4, int inDim, int outDim, int percentLoad, int numExperts, int rowPitchBytes) {
+    return check_bundle(q4 ? kQ4 : kFp16, inDim, outDim, percentLoad, numExperts, rowPitchBytes, nullptr);
+}
 
 // The multiply accumulates in fixed point; its scale needs a bound on the weights: per expert, the sum over ranks
 // of the largest |w| of that rank (Q4: of the largest row mean).  One pass over the buckets at registration.
@@ -422,16 +453,15 @@ extern "C" int effort_aligned_row_pitch(int outDim) {
 extern "C" effort_w* effort_weights_fp16_pitched(effort_ctx* c, const void* buckets, int rowPitchBytes, const void* stats, const void* probes,
                                                  int inDim, int outDim, int percentLoad, int numExperts) {
     if (!c || !buckets || !stats || !probes) { fail(c, EFFORT_ERR_ARG, "effort_weights_fp16: null argument"); return nullptr; }
-    const int pitch = rowPitchBytes ? rowPitchBytes : (outDim > 0 ? outDim / 16 * 2 : 0);
-    if (inDim <= 0 || outDim <= 0 || percentLoad < 1 || percentLoad > 16 || numExperts < 1 || check_shape(inDim, outDim) != EFFORT_OK ||
-        inDim > 65535 || pitch < outDim / 16 * 2 || pitch % 4 || (size_t)numExperts * percentLoad * inDim * pitch > 0xFFFFFFFFull) {
-        fail(c, EFFORT_ERR_SHAPE, "effort_weights_fp16: unsupported shape or row pitch (a multiple of 4 bytes >= 2*cols; buckets < 4 GiB)"); return nullptr; }
+    uint32_t pitch = 0;
+    if (check_bundle(kFp16, inDim, outDim, percentLoad, numExperts, rowPitchBytes, &pitch) != EFFORT_OK) {     // (before anything is read or allocated)
+        fail(c, EFFORT_ERR_SHAPE, "effort_weights_fp16: unsupported shape or row pitch (a multiple of 4 bytes >= 2*cols; buckets < 4 GiB; stats, 8 bytes a bucket row, < 4 GiB)"); return nullptr; }
     effort_w* w = new (std::nothrow) effort_w();
     if (!w) return nullptr;
     w->ctx = c; w->fmt = kFp16;
     w->buckets = static_cast<const uint16_t*>(buckets); w->stats = stats; w->probes = static_cast<const uint16_t*>(probes);
     w->inDim = inDim; w->outDim = outDim; w->rowsPerIn = percentLoad; w->numExperts = numExperts; w->cols = outDim / 16;
-    w->bucketsSrc = w->buckets; w->rowPitch = w->srcPitch = (uint32_t)pitch;
+    w->bucketsSrc = w->buckets; w->rowPitch = w->srcPitch = pitch;
     if (register_bound(c, w) != EFFORT_OK) { effort_weights_free(w); return nullptr; }
     return w;
 }
@@ -443,9 +473,8 @@ extern "C" effort_w* effort_weights_fp16(effort_ctx* c, const void* buckets, con
 extern "C" effort_w* effort_weights_q4(effort_ctx* c, const void* buckets, const void* stats, const void* probes,
                                        const void* outliers, int64_t nOutliers, int inDim, int outDim, int numExperts) {
     if (!c || !buckets || !stats || !probes) { fail(c, EFFORT_ERR_ARG, "effort_weights_q4: null argument"); return nullptr; }
-    if (inDim <= 0 || outDim <= 0 || numExperts < 1 || check_shape(inDim, outDim) != EFFORT_OK || outDim % 32 || inDim > 65535 ||
-        nOutliers < 0 || (size_t)numExperts * 8 * inDim * (outDim / 32) * 2 > 0xFFFFFFFFull) {
-        fail(c, EFFORT_ERR_SHAPE, "effort_weights_q4: unsupported shape (or buckets >= 4 GiB)"); return nullptr; }
+    if (nOutliers < 0 || check_bundle(kQ4, inDim, outDim, 8, numExperts, 0, nullptr) != EFFORT_OK) {           // (before anything is read or allocated)
+        fail(c, EFFORT_ERR_SHAPE, "effort_weights_q4: unsupported shape (or buckets >= 4 GiB, or stats, 8 bytes a bucket row, >= 4 GiB)"); return nullptr; }
     effort_w* w = new (std::nothrow) effort_w();
     if (!w) return nullptr;
     w->ctx = c; w->fmt = kQ4;

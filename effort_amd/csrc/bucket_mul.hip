@@ -295,6 +295,7 @@ __device__ __forceinline__ void stage_issue(const GroupKArgs& ga, const ItemRef&
     const uint32_t rowsPerIn = g.rowsPerIn, inDim = g.inDim, mask = (1u << lg) - 1u;
     const uint32_t nSlots = FMT == kFp16 ? (rowsPerIn << lg) : (nb << 3);
     constexpr bool compact = COMPACT && FMT == kFp16;              // a.stats = the row means alone, u16 per bucket row (persistent launches)
+    // (32-bit size and, below, 32-bit byte offsets: registration bounds the whole stack's stats, 8 bytes a bucket row, below 4 GiB -- api.hip, check_bundle)
     const u32x4 rs = make_rsrc(a.stats, (uint32_t)((size_t)g.numExperts * g.expertRows * (compact ? 2u : 8u)));
     const u32x4 rv = make_rsrc(a.v, inDim * 4u);
     const uint32_t ldsM = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lds_v*)(smem + lp.offM));

@@ -104,6 +104,10 @@ EFFORT_API const char* effort_version(void);
  *   stats   f16 [numExperts][inDim*percentLoad][4]           mean|row| in all four lanes (.w is read)
  *   probes  f16 [numExperts][4096]
  * percentLoad (1..16) = rank slices present per expert (loader.swift:50, expertSize = percentLoad*inDim).
+ * Accepted sizes (anything else: NULL, EFFORT_ERR_SHAPE, nothing read): 4096 <= inDim <= 65535 (odd ones included), outDim a multiple of 32
+ * up to 16384, and -- the multiply addresses every per-row array with 32-bit offsets -- with rows = numExperts * percentLoad * inDim
+ * bucket rows in the whole stack: buckets (rows * row pitch) < 4 GiB AND stats (rows * 8 bytes) < 4 GiB, i.e. rows < 2^29.  The second
+ * limit is the tighter one only where a bucket row is shorter than 8 bytes (outDim 32; Q4: outDim 32, 64, 96).
  * Pointers are BORROWED: the caller keeps the buffers alive while the handle is in use.  Registration reads the
  * buckets once (max |w| of every bucket row, which bounds the multiply's fixed-point accumulators): fill the
  * buffers BEFORE registering, and register again if their contents change. */

@@ -61,6 +61,10 @@ EFFORT_API int effort_debug_plan(int q4, int numCU, int lanes, int n, const int*
                       const int* prologue, const int* hasResid, const double* effort, int persistent, int tuneW, int tuneE, int tuneS,
                       int* we, int* slices, int* tiles, int* sliceRows, int* launchOf,
                       int* launchPersistent, int* launchCutJobs, int* launchCompact, int* launchStagger);
+/* What registration answers for a bundle's SIZES alone -- effort_weights_fp16_pitched (q4 = 0) / effort_weights_q4 (q4 = 1: percentLoad is
+ * ignored, rowPitchBytes must be 0) -- before it reads or allocates anything: EFFORT_OK or EFFORT_ERR_SHAPE.  The limits of effort_hip.h
+ * ("weights"): the shape rule, and every per-row array of the stack below 4 GiB.  No context, no device, no HIP call. */
+EFFORT_API int effort_debug_check_bundle(int q4, int inDim, int outDim, int percentLoad, int numExperts, int rowPitchBytes);
 /* The instantiations of the multiply kernel that exist for a format (q4 = 0: FP16), as rows of five ints {waves per workgroup, columns per
  * lane, fused (prologue / residual), compact (FP16: compact row means), lean (the plain-grid instantiation)}: the list the device preparation
  * and the launch selection walk (bucket_mul.hip: EFFORT_GEOMS x each_variant).  No context, no device, no HIP call.  Fills at most maxRows rows

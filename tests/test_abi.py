@@ -101,6 +101,73 @@ def test_null_arguments_are_reported_not_crashed(hip_lib_built):
     assert lib.effort_last_error(None) == b"null context"
 
 
+# ---- registration bounds every per-row array of a stack (csrc/api.hip: check_bundle) -------------------------------------------------
+# The multiply reaches the buckets, the stats (8 bytes a bucket row) and the compact means (2 bytes) through 32-bit descriptors and byte
+# offsets.  Where a bucket row is shorter than 8 bytes -- FP16 outDim 32 (4 bytes); Q4 outDim 32, 64, 96 (2, 4, 6 bytes) -- the stats are
+# the larger array, and a stack whose buckets stay below 4 GiB can hold stats past it: such a handle used to be accepted, its
+# descriptor's size truncated, and the rows behind it read as mean 0 -- never selected, silently.
+# (q4, inDim, outDim, percentLoad, numExperts) -> what registration answers, each refusal with the accepted neighbour beside it.
+OK, SHAPE = 0, -2
+BUNDLE_SIZES = [
+    ((0, 65535, 32, 16, 600), SHAPE),         # buckets 2.5 GB, stats 5.0 GB
+    ((0, 65535, 32, 16, 512), OK),            # rows * 8 = 4 294 901 760: the most experts of that shape
+    ((0, 65535, 32, 16, 513), SHAPE),
+    ((0, 65535, 64, 16, 512), OK),            # 8-byte rows: both limits meet
+    ((0, 65535, 64, 16, 513), SHAPE),
+    ((1, 65535, 64, 8, 1025), SHAPE),         # Q4, 4-byte rows: the buckets alone allow 2048 experts
+    ((1, 65535, 64, 8, 1024), OK),
+    ((1, 65535, 32, 8, 1025), SHAPE), ((1, 65535, 96, 8, 1025), SHAPE), ((1, 65535, 96, 8, 1024), OK),
+    ((1, 65535, 128, 8, 1024), OK), ((1, 65535, 128, 8, 1025), SHAPE),       # 8-byte rows again
+    # accepted before and still legal: the bucket limit is the one that binds from 8-byte rows on
+    ((0, 4096, 16384, 16, 31), OK), ((0, 4096, 16384, 16, 32), SHAPE),       # 31 x 128 MiB (tests/test_gpu_edge_shapes.py runs it); 32 = 4 GiB
+    ((0, 4096, 11008, 16, 1), OK), ((0, 14336, 4096, 16, 8), OK), ((1, 4096, 11008, 8, 32), OK), ((0, 4097, 32, 1, 1), OK),
+    # the shape rule itself
+    ((0, 4095, 32, 16, 1), SHAPE), ((0, 65536, 32, 16, 1), SHAPE), ((0, 4096, 48, 16, 1), SHAPE), ((0, 4096, 16416, 16, 1), SHAPE),
+    ((0, 4096, 32, 0, 1), SHAPE), ((0, 4096, 32, 17, 1), SHAPE), ((0, 4096, 32, 16, 0), SHAPE), ((1, 4096, 16, 8, 1), SHAPE),
+]
+
+
+def test_registration_bounds_every_per_row_array(hip_lib_built):
+    import effort_amd
+    lib = effort_amd.lib()
+    for (q4, inDim, outDim, load, experts), want in BUNDLE_SIZES:
+        assert lib.effort_debug_check_bundle(q4, inDim, outDim, load, experts, 0) == want, (q4, inDim, outDim, load, experts)
+        rows, pitch = experts * load * inDim, outDim // (32 if q4 else 16) * 2
+        if want == OK:
+            assert rows * pitch < 2 ** 32 and rows * 8 < 2 ** 32
+    # the FP16 row pitch: a multiple of 4 bytes, not below the dense rows, and the PITCHED buckets below 4 GiB
+    assert lib.effort_debug_check_bundle(0, 4096, 64, 16, 1, 128) == OK
+    assert lib.effort_debug_check_bundle(0, 4096, 64, 16, 1, 6) == SHAPE and lib.effort_debug_check_bundle(0, 4096, 64, 16, 1, 10) == SHAPE
+    assert lib.effort_debug_check_bundle(0, 65535, 32, 16, 32, 128) == OK and lib.effort_debug_check_bundle(0, 65535, 32, 16, 33, 128) == SHAPE
+    assert lib.effort_debug_check_bundle(1, 4096, 64, 8, 1, 128) == SHAPE          # (Q4 rows are dense)
+
+
+@pytest.mark.gpu
+def test_registration_refuses_oversized_stats_before_reading(hip_lib_built):
+    """The entry points themselves, on small dummy device buffers: a stack whose stats would pass 4 GiB comes back NULL with the shape error
+    -- check_bundle runs right behind the null checks, before the handle exists and before the first kernel of registration, so nothing of
+    the (far too small) buffers is read; the accepted neighbour of each is not registered here (it would read gigabytes)."""
+    import torch
+
+    import effort_amd
+    lib, g = effort_amd.lib(), effort_amd.gpu(0)
+    dummy = torch.zeros(4096, dtype=torch.int16, device="cuda:0")
+    p = ctypes.c_void_p(dummy.data_ptr())
+    g._bind_stream()
+    for (q4, inDim, outDim, load, experts), want in BUNDLE_SIZES:
+        if want == OK:
+            continue
+        if q4:
+            h = lib.effort_weights_q4(g.ctx, p, p, p, None, 0, inDim, outDim, experts)
+        else:
+            h = lib.effort_weights_fp16(g.ctx, p, p, p, inDim, outDim, load, experts)
+        assert not h, (q4, inDim, outDim, load, experts)
+        err = lib.effort_last_error(g.ctx)
+        assert b"unsupported shape" in err and b"stats" in err, err
+    g.eval()
+    assert int(dummy.abs().sum()) == 0
+
+
 def test_shipped_library_reads_no_environment(hip_lib_built):
     """The A/B switches of the lab builds (-DEFFORT_LAB: EFFORT_ABLATE, EFFORT_NO_CUTJOBS ...) are compiled out of the shipped
     library: no EFFORT_* variable name is left in it, and no object of the call path imports getenv (the one import left

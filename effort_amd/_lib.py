@@ -93,6 +93,11 @@ _SIGS = {
     "effort_mix2_add": (C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     "effort_dense_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int]),
     "effort_dense_gemv_expert": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "effort_dense_gemm_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "effort_fetch_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int]),
+    "effort_add_rmsnorm_mul_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
+    "effort_rope_kv_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "effort_attention_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "effort_set_dense_backend": (C.c_int, [_P, C.c_int]),
     "effort_last_dispatch_count": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "effort_last_cutoff": (C.c_int, [_P, C.POINTER(C.c_float)]),

@@ -56,6 +56,10 @@ struct effort_ctx {
     uint32_t* d_blockScratch = nullptr;
     uint16_t* d_vhalf = nullptr;      // v.asFloat16() for the dense baseline
     size_t vhalfElems = 0;
+    uint16_t* d_xhRows = nullptr;     // effort_dense_gemm_rows: f16(x) of a block.  Its OWN scratch: d_vhalf's address sits in captured token steps (rocBLAS backend)
+    size_t xhRowsElems = 0;
+    float* d_gemmPart = nullptr;      // effort_dense_gemm_rows: the k splits' partial sums
+    size_t gemmPartFloats = 0;
     float* d_cos = nullptr;
     uint16_t* d_convVals = nullptr;   // converter scratch (transposed matrix)
     size_t convElems = 0;
@@ -366,7 +370,7 @@ extern "C" void effort_destroy(effort_ctx* c) {
     if (c->ev) { for (int i = 0; i < effort_ctx::kMaxSamples * 4; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]); delete[] c->ev; }
     for (int i = 0; i < effort_ctx::kMaxLanes; i++) lane_free(c->device, c->lane[i]);
     pool_put(c->device, c->forkEv);
-    hipFree(c->d_blockScratch); hipFree(c->d_vhalf); hipFree(c->d_cos); hipFree(c->d_convVals); hipFree(c->d_status); hipFree(c->d_tstamp);
+    hipFree(c->d_blockScratch); hipFree(c->d_vhalf); hipFree(c->d_xhRows); hipFree(c->d_gemmPart); hipFree(c->d_cos); hipFree(c->d_convVals); hipFree(c->d_status); hipFree(c->d_tstamp);
     delete c;
 }
 
@@ -1062,6 +1066,71 @@ extern "C" int effort_fetch_row(effort_ctx* c, const void* emb, const uint32_t* 
     if (!c || !emb || !id || !out || n <= 0) return fail(c, EFFORT_ERR_ARG, "fetch_row: bad argument");
     { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
     HIP_TRY(c, launch_fetch_row(static_cast<const uint16_t*>(emb), id, out, (uint32_t)n, c->stream));
+    return EFFORT_OK;
+}
+// ---- prompt prefill (prefill.hip): a block of tokens per call.  pos0 and rows are HOST values (prefill is eager, never captured), so
+// every refusal is a return code with nothing enqueued; the values are judged before the pointers, the lanes are joined before the launch.
+static_assert(EFFORT_PREFILL_MAX_ROWS == 64, "prefill.hip: kPrefillMaxRows, four token tiles of 16");
+static bool prefill_rows_ok(int rows) { return rows >= 1 && rows <= EFFORT_PREFILL_MAX_ROWS; }
+extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float* x, float* out, int inDim, int outDim, int rows) {
+    if (inDim <= 0 || outDim <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows: inDim, outDim >= 1, 1 <= rows <= 64");
+    if (!dense_gemm_rows_supported((uint32_t)inDim, (uint32_t)outDim))
+        return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, W below 4 GiB");
+    if (!c || !W || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    if ((size_t)rows * inDim > c->xhRowsElems) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        hipFree(c->d_xhRows); c->d_xhRows = nullptr; c->xhRowsElems = 0;
+        const size_t want = (size_t)EFFORT_PREFILL_MAX_ROWS * inDim;                 // (a block's worth: the next, longer block does not allocate again)
+        HIP_TRY(c, hipMalloc(&c->d_xhRows, want * 2));
+        c->xhRowsElems = want;
+    }
+    if (dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows) > c->gemmPartFloats) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        hipFree(c->d_gemmPart); c->d_gemmPart = nullptr; c->gemmPartFloats = 0;
+        const size_t want = dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS);
+        HIP_TRY(c, hipMalloc(&c->d_gemmPart, want * sizeof(float)));
+        c->gemmPartFloats = want;
+    }
+    HIP_TRY(c, launch_dense_gemm_rows(static_cast<const uint16_t*>(W), x, c->d_xhRows, c->d_gemmPart, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows,
+                                      c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_fetch_rows(effort_ctx* c, const void* emb, const uint32_t* ids, float* out, int n, int rows) {
+    if (n <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "fetch_rows: n >= 1, 1 <= rows <= 64");
+    if (!c || !emb || !ids || !out) return fail(c, EFFORT_ERR_ARG, "fetch_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_fetch_rows(static_cast<const uint16_t*>(emb), ids, out, (uint32_t)n, (uint32_t)rows, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_add_rmsnorm_mul_rows(effort_ctx* c, float* h, const float* delta, const void* w, float* out, int n, int rows) {
+    if (n <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "add_rmsnorm_mul_rows: n >= 1, 1 <= rows <= 64");
+    if (!c || !h || !w || !out) return fail(c, EFFORT_ERR_ARG, "add_rmsnorm_mul_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_add_rmsnorm_mul_rows(h, delta, static_cast<const uint16_t*>(w), out, (uint32_t)n, (uint32_t)rows, c->stream));
+    return EFFORT_OK;
+}
+static bool prefill_range_ok(int pos0, int rows, int maxTokens) {
+    return prefill_rows_ok(rows) && pos0 >= 0 && maxTokens > 0 && pos0 <= maxTokens - rows;
+}
+extern "C" int effort_rope_kv_rows(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache,
+                                   int pos0, int rows, int numHeads, int numHeadsKV, int headDim, int maxTokens, float ropeBase) {
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return fail(c, EFFORT_ERR_ARG, "rope_kv_rows: 1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (numHeads <= 0 || numHeadsKV <= 0 || numHeads % numHeadsKV || headDim < 2 || headDim > 1024 || headDim % 2 || !(ropeBase > 1.0f))
+        return fail(c, EFFORT_ERR_SHAPE, "rope_kv_rows: bad head geometry");
+    if (!c || !xq || !xk || !xv || !qOut || !kCache || !vCache) return fail(c, EFFORT_ERR_ARG, "rope_kv_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_rope_kv_rows(xq, xk, xv, qOut, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, numHeads, numHeadsKV, headDim, ropeBase, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_attention_rows(effort_ctx* c, const float* q, const float* kCache, const float* vCache, int pos0, int rows, float* out,
+                                     int numHeads, int headDim, int maxTokens) {
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return fail(c, EFFORT_ERR_ARG, "attention_rows: 1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (numHeads <= 0 || maxTokens > 8192 || (headDim != 64 && headDim != 128 && headDim != 256))
+        return fail(c, EFFORT_ERR_SHAPE, "attention_rows: headDim 64/128/256, maxTokens <= 8192");
+    if (!c || !q || !kCache || !vCache || !out) return fail(c, EFFORT_ERR_ARG, "attention_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_attention_rows(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream));
     return EFFORT_OK;
 }
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {

@@ -1,0 +1,360 @@
+// Prompt prefill: the dense path for a BLOCK of tokens (up to kPrefillMaxRows = EFFORT_PREFILL_MAX_ROWS), beside the token step.
+// A GEMV-per-token loop streams every weight from HBM once per prompt token; the tokens of a prompt are independent inside a
+// layer's multiplies, so a block of them can share one pass over each matrix.
+//
+//   dense_gemm_rows   out[r] = W * f16(x[r]) for rows r of a block: basicMul's arithmetic (helpers/mps.swift:14-47: x rounded to f16
+//                     once, exact f16 products, f32 sums) on v_mfma_f32_16x16x32_f16.  An MFMA tile is 16 rows of W (A operand) by 16
+//                     tokens (B operand); up to four token tiles share every weight fragment.
+//   *_rows            block forms of the glue (decode.hip): fetch_row, add_rmsnorm_mul, rope_kv, attention, one workgroup (or one
+//                     grid row) per token of the block, the SAME sums in the same order -- per token they write the bits of the
+//                     single-token kernels, which are pinned to float64 references (tests/test_gpu_glue.py).
+//
+// The block multiply.  The weight stream is what it is bound by, and a lane's A fragment is 16 contiguous bytes of a weight row, so
+// weights go from global memory straight into the MFMA operand -- no LDS.  K is walked in stages of kPfStage = 256 elements; inside
+// each 64-element chunk (one 128-byte line of each row) lane group g = lane >> 4 takes elements 16g .. 16g+15 as the fragments of
+// TWO MFMA steps (u = 0, 1: elements 16g + 8u + j), so the four lanes of a row cover a whole line with two 16-byte loads each.  The
+// B operand takes the same permutation: 16 contiguous bytes of f16(x[token]).
+// f16(x) is written ONCE per call by rows_to_f16_kernel into context scratch (64 x 14336 halves are 1.8 MB: no LDS holds that).  A
+// workgroup is kPfWaves = 4 waves on four consecutive 16-row tiles (64 rows of W) and the SAME k range: a stage of f16(x) (up to 64
+// tokens x 256 elements, 32 KB) is staged in LDS once per workgroup -- double-buffered, the next stage's token pieces and the next
+// stage's weight fragments (8 loads per lane) asked for before the current stage is multiplied -- and read by all four waves.
+// 64 rows per workgroup are too few workgroups for the chip (64 for 4096 rows), so K is also split over blockIdx.y into `splits`
+// ranges of whole stages; with more than one split every range writes its partial sums to context scratch and reduce_splits_kernel
+// adds them.
+// Measured at 64 rows, us per call on 4096 x 4096 / 4096 -> 14336 (profiles/r09_prefill.json; the GEMV: 8.1 / 21.0): this tiling
+// 19.7 / 50.1; eight waves on 128 rows with 128-element stages 22.6 / 58.6; the first version -- a workgroup of 16 rows whose eight
+// waves split K, every wave reading its token fragments from L2 (128 MB of L2 reads beside a 32 MB matrix) -- 25.7 / 83.4.
+//
+// The order of the sums does not depend on the number of rows: `splits` and the stages of a split follow from (inDim, outDim) alone;
+// element (row, token) is the sum over the splits s = 0, 1, ..., in that order, of an accumulator that took its split's MFMA steps in
+// ascending stage, chunk, u order.  A token column that is not live is a zero operand (zeros are staged for it: no x row at or
+// beyond `rows` is read, nor the scratch's stale halves); a k step past inDim multiplies zeros.  So a row's bits are the same for
+// every `rows` and every position in the block.
+#include "effort_internal.h"
+
+namespace effort {
+
+constexpr int kPrefillMaxRows = 64;       // == EFFORT_PREFILL_MAX_ROWS (api.hip asserts it)
+constexpr int kPfWaves = 4;               // waves per workgroup: one 16-row tile of W each
+constexpr uint32_t kPfStage = 256;        // k elements per stage: 8 16-byte weight loads per lane
+constexpr int kPfChunks = kPfStage / 64;  // 64-element chunks (128-byte lines of a row) per stage
+constexpr uint32_t kPfQ = kPfStage / 8;   // 16-byte pieces of a token row per stage
+constexpr uint32_t kPfPitch = kPfStage / 8 + 1;   // uint4 per staged token row: 256 bytes + 16 of padding (a 256-byte pitch puts every token on the same banks)
+constexpr uint32_t kPfMaxSplits = 16, kPfTargetGroups = 256;
+constexpr size_t kPfKeepBytes = 64u << 20;   // == kGemvKeepBytes (gemv.hip): a larger matrix is streamed nt, for the reason given there
+
+typedef _Float16 pf_half8 __attribute__((ext_vector_type(8)));
+typedef float pf_f32x4 __attribute__((ext_vector_type(4)));
+
+// x.asFloat16() (mps.swift:19) of the live rows, once per call
+__global__ void rows_to_f16_kernel(const float* __restrict__ x, uint16_t* __restrict__ xh, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) xh[i] = __half_as_ushort(__float2half_rn(x[i]));
+}
+
+// out[i] = part[0][i] + part[1][i] + ... in that order
+__global__ void reduce_splits_kernel(const float* __restrict__ part, float* __restrict__ out, uint32_t n, uint32_t splits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s = part[i];
+    for (uint32_t k = 1; k < splits; k++) s += part[(size_t)k * n + i];
+    out[i] = s;
+}
+
+// The k split of a shape: stages per split and the number of splits (a function of the shape alone -- never of rows).
+struct PfSplit { uint32_t per, splits; };
+static PfSplit pf_split(uint32_t inDim, uint32_t outDim) {
+    const uint32_t stages = (inDim + kPfStage - 1u) / kPfStage, groups = (outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves);
+    uint32_t want = (kPfTargetGroups + groups - 1u) / groups;
+    if (want > kPfMaxSplits) want = kPfMaxSplits;
+    if (want > stages) want = stages;
+    const uint32_t per = (stages + want - 1u) / want;
+    return PfSplit{per, (stages + per - 1u) / per};
+}
+
+// NT = token tiles (of 16) of the block; AUX = cache policy of the weight loads (0, or 2 = nt).  grid = (groups of 16 * kPfWaves = 64 rows, splits).
+// dst = out when there is one split, else the partial sums [splits][rows][outDim].
+template <int NT, int AUX>
+__global__ __launch_bounds__(64 * kPfWaves, 2) void dense_gemm_rows_kernel(const uint16_t* __restrict__ W, const uint16_t* __restrict__ xh,
+                                                                           float* __restrict__ dst, uint32_t inDim, uint32_t outDim, uint32_t rows,
+                                                                           uint32_t per) {
+    __shared__ uint4 xs[2][NT * 16][kPfPitch];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t g = lane >> 4, r16 = lane & 15u, row0 = (blockIdx.x * kPfWaves + wave) * 16u;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(W), 0, (int)min((size_t)0xFFFFFFFFu, (size_t)outDim * inDim * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(xh), 0, (int)(rows * inDim * 2u), 0x00020000);
+    const uint32_t aOff = min(row0 + r16, outDim - 1u) * inDim * 2u;           // a row past the end re-reads the last one (W < 4 GiB)
+    const uint32_t stages = (inDim + kPfStage - 1u) / kPfStage;
+    const uint32_t s0 = blockIdx.y * per, s1 = min(s0 + per, stages);           // (the host made every split non-empty)
+    // staging: thread `tid` moves 16-byte piece q = idx % kPfQ of token idx / kPfQ, idx = tid + 64 kPfWaves i
+    constexpr int kPieces = (NT * 16 * kPfQ + 64 * kPfWaves - 1) / (64 * kPfWaves);
+    uint4 nextB[kPieces], curA[kPfChunks][2], nextA[kPfChunks][2];
+    auto ask_b = [&](uint32_t s) {
+#pragma unroll
+        for (int i = 0; i < kPieces; i++) {
+            const uint32_t idx = tid + i * 64u * kPfWaves, tok = idx / kPfQ, e = s * kPfStage + (idx % kPfQ) * 8u;
+            const auto x = __builtin_amdgcn_raw_buffer_load_b128(xr, min(tok, rows - 1u) * inDim * 2u + min(e, inDim - 8u) * 2u, 0, 0);    // clamped: masked in put_b
+            nextB[i] = make_uint4(x[0], x[1], x[2], x[3]);
+        }
+    };
+    auto put_b = [&](uint32_t s, uint32_t buf) {       // (the masks are applied HERE, not beside the loads: a use right behind a load makes it wait)
+#pragma unroll
+        for (int i = 0; i < kPieces; i++) {
+            const uint32_t idx = tid + i * 64u * kPfWaves, tok = idx / kPfQ, e = s * kPfStage + (idx % kPfQ) * 8u;
+            const uint32_t m = (tok < rows && e < inDim) ? 0xFFFFFFFFu : 0u;    // a dead column, a k past inDim: zeros are staged
+            if (idx < NT * 16u * kPfQ) xs[buf][tok][idx % kPfQ] = make_uint4(nextB[i].x & m, nextB[i].y & m, nextB[i].z & m, nextB[i].w & m);
+        }
+    };
+    auto ask_a = [&](uint32_t s, uint4 (&a)[kPfChunks][2]) {
+#pragma unroll
+        for (int c = 0; c < kPfChunks; c++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const uint32_t e = s * kPfStage + c * 64u + g * 16u + u * 8u;
+                const auto w = __builtin_amdgcn_raw_buffer_load_b128(rs, aOff + min(e, inDim - 8u) * 2u, 0, AUX);   // clamped, branch-free (inDim % 32 == 0)
+                a[c][u] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+    };
+    pf_f32x4 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; t++) acc[t] = pf_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    ask_a(s0, curA);
+    ask_b(s0);
+    put_b(s0, 0);
+    __syncthreads();
+    for (uint32_t s = s0; s < s1; s++) {                                          // (uniform)
+        const uint32_t buf = (s - s0) & 1u;
+        const bool more = s + 1u < s1;
+        if (more) { ask_a(s + 1u, nextA); ask_b(s + 1u); }                        // the next stage's loads run under this stage's products
+        __builtin_amdgcn_sched_barrier(0);             // (left to itself the scheduler sinks the loads to their first use)
+#pragma unroll
+        for (int c = 0; c < kPfChunks; c++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const uint32_t m = s * kPfStage + c * 64u + g * 16u + u * 8u < inDim ? 0xFFFFFFFFu : 0u;    // a clamped lane holds a copy of other data: a zero operand
+                const pf_half8 af = __builtin_bit_cast(pf_half8, make_uint4(curA[c][u].x & m, curA[c][u].y & m, curA[c][u].z & m, curA[c][u].w & m));
+#pragma unroll
+                for (int t = 0; t < NT; t++) {
+                    const pf_half8 bf = __builtin_bit_cast(pf_half8, xs[buf][t * 16 + r16][c * 8 + g * 2 + u]);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc[t], 0, 0, 0);
+                }
+            }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) {
+            put_b(s + 1u, buf ^ 1u);                        // (read last in the stage before this one: every wave passed that stage's barrier)
+#pragma unroll
+            for (int c = 0; c < kPfChunks; c++)
+#pragma unroll
+                for (int u = 0; u < 2; u++) curA[c][u] = nextA[c][u];
+        }
+        __syncthreads();
+    }
+    // Accumulator register i of lane l is W row 4 * (l >> 4) + i, token l & 15.
+    float* o = dst + (size_t)blockIdx.y * rows * outDim;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+        const uint32_t tok = t * 16u + r16;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t row = row0 + g * 4u + i;
+            if (tok < rows && row < outDim) o[(size_t)tok * outDim + row] = acc[t][i];
+        }
+    }
+}
+
+bool dense_gemm_rows_supported(uint32_t inDim, uint32_t outDim) {
+    return inDim % 32u == 0 && inDim >= 32u && inDim <= 65536u && outDim >= 1u && outDim <= (1u << 24) && (size_t)outDim * inDim * 2u <= 0xFFFFFFFFull;
+}
+// floats of context scratch the partial sums of a call need (0: one split, the kernel writes out itself)
+size_t dense_gemm_rows_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows) {
+    const PfSplit sp = pf_split(inDim, outDim);
+    return sp.splits > 1u ? (size_t)sp.splits * rows * outDim : 0;
+}
+
+template <int NT, int AUX>
+static hipError_t launch_dense_gemm_rows_t(const uint16_t* W, const uint16_t* xh, float* dst, uint32_t inDim, uint32_t outDim, uint32_t rows,
+                                           PfSplit sp, hipStream_t st) {
+    hipLaunchKernelGGL((dense_gemm_rows_kernel<NT, AUX>), dim3((outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves), sp.splits), dim3(64 * kPfWaves), 0, st,
+                       W, xh, dst, inDim, outDim, rows, sp.per);
+    return hipGetLastError();
+}
+
+// xh: scratch of rows * inDim halves; part: scratch of dense_gemm_rows_partial_floats floats
+hipError_t launch_dense_gemm_rows(const uint16_t* W, const float* x, uint16_t* xh, float* part, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows,
+                                  hipStream_t st) {
+    if (rows < 1u || rows > (uint32_t)kPrefillMaxRows) return hipErrorInvalidValue;
+    const uint32_t n = rows * inDim;
+    hipLaunchKernelGGL(rows_to_f16_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, x, xh, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const PfSplit sp = pf_split(inDim, outDim);
+    float* dst = sp.splits > 1u ? part : out;
+    const bool nt = (size_t)inDim * outDim * 2u > kPfKeepBytes;
+    switch ((rows + 15u) / 16u) {
+        case 1: e = nt ? launch_dense_gemm_rows_t<1, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<1, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
+        case 2: e = nt ? launch_dense_gemm_rows_t<2, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<2, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
+        case 3: e = nt ? launch_dense_gemm_rows_t<3, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<3, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
+        default: e = nt ? launch_dense_gemm_rows_t<4, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<4, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
+    }
+    if (e != hipSuccess || sp.splits == 1u) return e;
+    const uint32_t no = rows * outDim;
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((no + 255u) / 256u), dim3(256), 0, st, part, out, no, sp.splits);
+    return hipGetLastError();
+}
+
+// ---- block forms of the glue -----------------------------------------------------------------------------------------------------
+// The sums of decode.hip, restated: block_sum / block_max (DPP scan inside a wave, then the waves' words in ascending order),
+// add_rmsnorm_mul_kernel's thread-strided squares, attention_kernel's wave-per-token dot with the xor butterfly, its softmax and
+// its phase sums.  Row r of a block is one workgroup (fetch: one grid row) running that code on its own slice of the operands.
+__device__ __forceinline__ float pf_block_sum(float x, float* red /* [17] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    x = wave_sum_f32(x);
+    __syncthreads();
+    if (lane == 0) red[wave] = x;
+    __syncthreads();
+    float s = 0.0f;
+    for (int w = 0; w < nw; w++) s += red[w];
+    return s;
+}
+__device__ __forceinline__ float pf_block_max(float x, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    x = wave_max_f32(x);
+    __syncthreads();
+    if (lane == 0) red[wave] = x;
+    __syncthreads();
+    float s = red[0];
+    for (int w = 1; w < nw; w++) s = fmaxf(s, red[w]);
+    return s;
+}
+
+// grid = (n / 256, rows)
+__global__ void fetch_rows_kernel(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ ids, float* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (i < n) out[(size_t)r * n + i] = half_bits_to_float(emb[(size_t)ids[r] * n + i]);
+}
+
+// grid = rows, block = 1024: add_rmsnorm_mul_kernel on row blockIdx.x of h, delta and out
+__global__ __launch_bounds__(1024) void add_rmsnorm_mul_rows_kernel(float* __restrict__ hAll, const float* __restrict__ deltaAll,
+                                                                    const uint16_t* __restrict__ w, float* __restrict__ outAll, uint32_t n) {
+    __shared__ float red[17];
+    float* h = hAll + (size_t)blockIdx.x * n;
+    const float* delta = deltaAll ? deltaAll + (size_t)blockIdx.x * n : nullptr;
+    float* out = outAll + (size_t)blockIdx.x * n;
+    constexpr int K = 4;
+    if (n <= K * 1024u) {
+        float x[K], d[K], wf[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const uint32_t i = min(k * 1024u + threadIdx.x, n - 1u);
+            x[k] = h[i];
+            d[k] = delta ? delta[i] : 0.0f;
+            wf[k] = half_bits_to_float(w[i]);
+        }
+        float ss = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const bool live = k * 1024u + threadIdx.x < n;
+            x[k] += d[k];
+            if (live && delta) h[k * 1024u + threadIdx.x] = x[k];
+            ss += live ? x[k] * x[k] : 0.0f;
+        }
+        const float inv = 1.0f / sqrtf(pf_block_sum(ss, red) / (float)n + 1e-5f);
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            if (k * 1024u + threadIdx.x < n) out[k * 1024u + threadIdx.x] = (x[k] * inv) * wf[k];
+        return;
+    }
+    float ss = 0.0f;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        float x = h[i];
+        if (delta) { x += delta[i]; h[i] = x; }
+        ss += x * x;
+    }
+    const float inv = 1.0f / sqrtf(pf_block_sum(ss, red) / (float)n + 1e-5f);
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = (h[i] * inv) * half_bits_to_float(w[i]);
+}
+
+// grid = (numHeads, rows), block = headDim: rope_kv_kernel on row blockIdx.y at position pos0 + blockIdx.y (the host checked the range)
+__global__ void rope_kv_rows_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
+                                    float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
+                                    uint32_t pos0, uint32_t numHeads, uint32_t kvRepeats, float logBase) {
+    const uint32_t head = blockIdx.x, r = blockIdx.y, d = threadIdx.x, headDim = blockDim.x, half = headDim / 2, pos = pos0 + r;
+    const uint32_t j = d % half;
+    const float freq = (float)exp((double)logBase * (-(double)j / (double)half));
+    const float angle = (float)pos * freq;
+    const float c = cosf(angle), s = sinf(angle);
+    const uint32_t kvDim = (numHeads / kvRepeats) * headDim;
+    const float* q = xq + (size_t)r * numHeads * headDim + head * headDim;
+    const float* k = xk + (size_t)r * kvDim + (head / kvRepeats) * headDim;
+    const float qr = d < half ? q[d] * c - q[d + half] * s : q[d] * c + q[d - half] * s;
+    const float kr = d < half ? k[d] * c - k[d + half] * s : k[d] * c + k[d - half] * s;
+    const size_t slot = ((size_t)pos * numHeads + head) * headDim + d;
+    qOut[(size_t)r * numHeads * headDim + head * headDim + d] = qr;
+    kCache[slot] = kr;
+    vCache[slot] = xv[(size_t)r * kvDim + (head / kvRepeats) * headDim + d];
+}
+
+// grid = (numHeads, rows), block = 256: attention_kernel on query row blockIdx.y over tokens 0 .. pos0 + blockIdx.y.  Every query
+// of the block reads its keys and values from the cache again (no sharing among the block's queries).
+__global__ __launch_bounds__(256) void attention_rows_kernel(const float* __restrict__ qAll, const float* __restrict__ kCache,
+                                                             const float* __restrict__ vCache, uint32_t pos0, float* __restrict__ outAll,
+                                                             uint32_t numHeads, uint32_t headDim) {
+    extern __shared__ float sc[];                      // [pos0 + rows] scores, then probabilities
+    __shared__ float red[17];
+    const uint32_t head = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, nTok = pos0 + r + 1u;
+    const float* qh = qAll + (size_t)r * numHeads * headDim + head * headDim;
+    float* out = outAll + (size_t)r * numHeads * headDim;
+    const float scale = 1.0f / sqrtf((float)headDim);
+    const int lane = tid & 63, wave = tid >> 6;
+    for (uint32_t t = wave; t < nTok; t += 4) {
+        const float* kh = kCache + ((size_t)t * numHeads + head) * headDim;
+        float dot = 0.0f;
+        for (uint32_t d = lane; d < headDim; d += 64) dot += qh[d] * kh[d];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) dot += __shfl_xor(dot, off);
+        if (lane == 0) sc[t] = dot * scale;
+    }
+    __syncthreads();
+    float m = -INFINITY;
+    for (uint32_t t = tid; t < nTok; t += 256) m = fmaxf(m, sc[t]);
+    m = pf_block_max(m, red);
+    float sum = 0.0f;
+    for (uint32_t t = tid; t < nTok; t += 256) { const float e = expf(sc[t] - m); sc[t] = e; sum += e; }
+    sum = pf_block_sum(sum, red);
+    const float inv = 1.0f / sum;
+    __shared__ float part[256];
+    const uint32_t d = tid % headDim, ph = tid / headDim, nph = 256 / headDim;
+    float acc = 0.0f;
+    if (ph < nph)
+        for (uint32_t t = ph; t < nTok; t += nph) acc += sc[t] * vCache[((size_t)t * numHeads + head) * headDim + d];
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < headDim) {
+        float s2 = 0.0f;
+        for (uint32_t p = 0; p < nph; p++) s2 += part[p * headDim + tid];
+        out[head * headDim + tid] = s2 * inv;
+    }
+}
+
+hipError_t launch_fetch_rows(const uint16_t* emb, const uint32_t* ids, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(fetch_rows_kernel, dim3((n + 255) / 256, rows), dim3(256), 0, st, emb, ids, out, n);
+    return hipGetLastError();
+}
+hipError_t launch_add_rmsnorm_mul_rows(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(add_rmsnorm_mul_rows_kernel, dim3(rows), dim3(1024), 0, st, h, delta, w, out, n);
+    return hipGetLastError();
+}
+hipError_t launch_rope_kv_rows(const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache, uint32_t pos0,
+                               uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, hipStream_t st) {
+    hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(numHeads, rows), dim3(headDim), 0, st, xq, xk, xv, qOut, kCache, vCache, pos0, numHeads,
+                       numHeads / numHeadsKV, logf(ropeBase));
+    return hipGetLastError();
+}
+hipError_t launch_attention_rows(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                 uint32_t numHeads, uint32_t headDim, hipStream_t st) {
+    hipLaunchKernelGGL(attention_rows_kernel, dim3(numHeads, rows), dim3(256), (pos0 + rows) * sizeof(float), st, q, kCache, vCache, pos0, out,
+                       numHeads, headDim);
+    return hipGetLastError();
+}
+
+}  // namespace effort

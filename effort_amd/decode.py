@@ -13,6 +13,10 @@ spends ~15 ms/token in such gaps, runNetwork.swift:91-103).  torch is used for b
 
 ``dense=True`` routes every projection through ``basicMul`` (rocBLAS GEMV on the f16 cores): the baseline the
 reference compares against (``effort`` 100 % vs dense, KL divergence of the logits).
+
+``Decoder.prefill`` / ``run(..., prefill=True)`` ingest a prompt in blocks of up to 64 tokens that share one pass over every
+matrix (the MFMA block multiply and the block forms of the glue, effort_amd/csrc/prefill.hip), eagerly, beside the token step:
+the step, its graphs and the cache layout are the same with or without it.
 """
 from __future__ import annotations
 
@@ -261,6 +265,8 @@ class Decoder:
         self.sample_params = Sampling().to_device(device=dev)     # effort_sample_params, 32 bytes: the sampled pick reads its settings HERE
         self._graphs: dict = {}
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
+        self._pf = None                                   # prefill's block buffers: made by the first ``prefill`` (see ``_prefill_buffers``)
+        self.last_prefill_s = None                        # run(prefill=True): synchronised wall time of its prefill
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
     def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None):
@@ -453,6 +459,91 @@ class Decoder:
             g.check(lib.effort_silu_mul(g.ctx, _p(x1), _p(x3), _p(x2), cfg.hiddenDim), "silu")
             mul(x2, L.w2.core, e, out)
 
+    # -- prompt prefill: a block of tokens per pass over the weights ---------------------------------------------------
+    PREFILL_MAX_ROWS = 64                                  # EFFORT_PREFILL_MAX_ROWS
+
+    def _prefill_buffers(self, chunk: int):
+        """The block buffers of ``prefill`` ([chunk, stateDim], [chunk, hiddenDim] and the rest), made on first use and again only for a
+        larger ``chunk``: a Decoder that never prefills holds none."""
+        if self._pf is not None and self._pf >= chunk:
+            return
+        cfg, dev = self.cfg, self.model.norm.device
+        f = lambda n: torch.zeros((chunk, n), dtype=torch.float32, device=dev)      # noqa: E731
+        q, kv = cfg.numHeads * cfg.headDim, cfg.numHeadsKV * cfg.headDim
+        self.pf_h, self.pf_norm = f(cfg.stateDim), f(cfg.stateDim)
+        self.pf_xq_temp, self.pf_xk_temp, self.pf_xv_temp, self.pf_xq = f(q), f(kv), f(kv), f(q)
+        self.pf_attnOutput, self.pf_attnFfnOut, self.pf_ffnOut = f(q), f(cfg.stateDim), f(cfg.stateDim)
+        self.pf_x1, self.pf_x3, self.pf_x2 = f(cfg.hiddenDim), f(cfg.hiddenDim), f(cfg.hiddenDim)
+        self.pf_ids = torch.zeros(chunk, dtype=torch.int32, device=dev)
+        self._pf = chunk
+
+    def _gemm_rows(self, x, core, out, rows: int):
+        """out[r] = core * f16(x[r]) for the first ``rows`` rows: ONE pass over the matrix (effort_dense_gemm_rows).  A matrix the block
+        kernel refuses (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMul`` row by row, as ``_dense_experts`` falls back."""
+        g = self.g
+        rc = _lib.lib().effort_dense_gemm_rows(g.ctx, _p(core), _p(x), _p(out), int(core.shape[1]), int(core.shape[0]), rows)
+        if rc == -2:
+            for r in range(rows):
+                basicMul(x[r], core, out[r])
+            return
+        g.check(rc, "dense_gemm_rows")
+
+    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64):
+        """Ingest prompt tokens in bulk: fill ``kCache`` / ``vCache`` rows ``pos0 .. pos0 + T - 1`` of every layer, in blocks of at most
+        ``chunk`` (<= 64) tokens that share ONE pass over each matrix, then set ``pos`` to ``pos0 + T``.  No logits, no pick: the next
+        ``token_step`` (or graph replay) continues from the caches.  Eager, never captured: ``pos0`` and the block sizes are host values.
+
+        The multiplies are the DENSE ones (``basicMul``'s arithmetic on every bundle's f16 ``core``, effort_dense_gemm_rows): the caches
+        hold dense K / V whatever effort the decode then runs at -- against a token-by-token ``dense=True`` ingest they differ by the
+        rounding of the f32 sums (another order), against an ingest at an effort by what that effort leaves out.  The glue is the
+        token step's, bit for bit per token (the *_rows entry points).  Per block and layer: norm (the pending residual added on its
+        way) -> wq, wk, wv -> rope + cache write -> attention over rows 0 .. its own -> wo -> norm -> w1, w3 -> silu -> w2; the last
+        layer stops after its cache write, since nothing behind it reaches a cache.
+
+        Raises ValueError, before anything is enqueued: a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
+        them), a Mixtral model, a column-sharded decoder, ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64."""
+        cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
+        ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
+        T = len(ids)
+        if self.moe or cfg.numExperts > 1:
+            raise ValueError("Decoder.prefill: dense-FFN models only (a Mixtral layer routes per token)")
+        if self.sharded:
+            raise ValueError("Decoder.prefill: not implemented for the column-sharded decode loop")
+        if any(getattr(L, w).core is None for L in m.layers for w in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")):
+            raise ValueError("Decoder.prefill: every bundle needs its f16 core (Model.random(keep_cores=True), or a Q4 model)")
+        if not 1 <= chunk <= self.PREFILL_MAX_ROWS:
+            raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
+        if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
+            raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
+        g._bind_stream()
+        self._prefill_buffers(chunk)
+        ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
+        rope = C.c_float(cfg.ropeBase)
+        for b0 in range(0, T, chunk):
+            rows, p = min(chunk, T - b0), pos0 + b0
+            self.pf_ids[:rows].copy_(torch.tensor(ids[b0:b0 + rows], dtype=torch.int32))
+            ck(lib.effort_fetch_rows(g.ctx, _p(m.tokEmbeddings), _p(self.pf_ids), _p(self.pf_h), cfg.stateDim, rows), "fetch_rows")
+            delta = None                                   # a product not yet added to h, exactly as in token_step
+            for n, L in enumerate(m.layers):
+                kc, vc = _p(self.kCache[n]), _p(self.vCache[n])
+                ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(delta), _p(L.attnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
+                for ew, out in ((L.wq, self.pf_xq_temp), (L.wk, self.pf_xk_temp), (L.wv, self.pf_xv_temp)):
+                    self._gemm_rows(self.pf_norm, ew.core, out, rows)
+                ck(lib.effort_rope_kv_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
+                                           cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
+                if n == len(m.layers) - 1:
+                    break                                  # nothing after the last layer's cache write reaches a cache
+                ck(lib.effort_attention_rows(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim,
+                                             self.maxTokens), "attention_rows")
+                self._gemm_rows(self.pf_attnOutput, L.wo.core, self.pf_attnFfnOut, rows)
+                ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
+                self._gemm_rows(self.pf_norm, L.w1.core, self.pf_x1, rows)
+                self._gemm_rows(self.pf_norm, L.w3.core, self.pf_x3, rows)
+                ck(lib.effort_silu_mul(g.ctx, _p(self.pf_x1), _p(self.pf_x3), _p(self.pf_x2), rows * cfg.hiddenDim), "silu")
+                self._gemm_rows(self.pf_x2, L.w2.core, self.pf_ffnOut, rows)
+                delta = self.pf_ffnOut
+        self.pos.fill_(pos0 + T)
+
     def _graph(self, effort: float, dense: bool, sampled: bool = False):
         key = ("dense",) if dense else (float(effort),)
         if sampled:                                              # the ONLY thing sampling adds to the key: its settings are device values
@@ -483,26 +574,40 @@ class Decoder:
         self.history.zero_()
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
-            collect_logits: bool = False, sampling=None):
+            collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
         (position, stream) under the seed) instead of the greedy one; the step graph is shared by all settings.
+        ``prefill``: the first P - 1 prompt tokens go through ``prefill`` (blocks of ``prefill_chunk`` tokens, one pass over the weights
+        per block, DENSE K / V in the caches whatever ``effort`` says) instead of P - 1 steps; step P - 1 -- the last prompt token --
+        and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
+        for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
+        holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
+        if prefill and forced:
+            raise ValueError("Decoder.run: prefill=True computes no logits for the prompt, forced=True wants them at every step")
         gr = self._graph(effort, dense, sampling is not None)
         self.reset()
         if sampling is not None:
             self.set_sampling(sampling)
         logits = []
         t0, timed = None, 0
-        for step in range(numTokens):
+        skip = min(len(tokenIds) - 1, numTokens) if prefill else 0
+        if skip:
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            self.prefill(tokenIds[:skip], 0, prefill_chunk)
+            torch.cuda.synchronize()
+            self.last_prefill_s = time.perf_counter() - tp
+        for step in range(skip, numTokens):
             if step < len(tokenIds):
                 self.tokId.fill_(int(tokenIds[step]))            # prompt (or forced) token; otherwise the previous pick stays
             elif forced:
                 break
-            if step == 2:
+            if step == max(2, skip):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
             gr.replay()
@@ -514,6 +619,7 @@ class Decoder:
         dt = (time.perf_counter() - t0) / timed if t0 is not None and timed else float("nan")
         steps = min(numTokens, len(tokenIds)) if forced else numTokens
         picked = self.history[:steps].cpu().tolist()
+        picked[:skip] = [-1] * skip                              # prefilled positions: nothing was picked there
         st = self.status()
         if st:
             raise RuntimeError(f"decode loop: device status {st} (1: a step past maxTokens / the history buffer, 2: NaN logits)")

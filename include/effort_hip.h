@@ -344,6 +344,45 @@ EFFORT_API int effort_argmax(effort_ctx* ctx, const float* logits_dev, int n, ui
  * bit 0 of the context's decode status; an argmax over NaN logits returns token 0 and raises bit 1.  Reads and clears it. */
 EFFORT_API int effort_decode_status(effort_ctx* ctx, int* host_out);
 
+/* ---- prompt prefill: a block of tokens shares one pass over the weights -------------------------
+ * The token step streams every matrix once per token.  These entry points take a BLOCK of 1 .. EFFORT_PREFILL_MAX_ROWS tokens: row r of
+ * every operand is token r of the block, rows contiguous.  pos0 and rows are HOST values -- prefill is eager and is never captured into
+ * a graph --, so every refusal is a return code with nothing enqueued and the decode status is not involved.  The argument VALUES are
+ * judged before the pointers (rows outside 1 .. 64, pos0 < 0, pos0 + rows > maxTokens, a dimension < 1: EFFORT_ERR_ARG; a shape the
+ * kernels do not serve: EFFORT_ERR_SHAPE; then a null pointer: EFFORT_ERR_ARG), and the lanes are joined before anything is launched. */
+#define EFFORT_PREFILL_MAX_ROWS 64
+
+/* out[r] = W * f16(x[r]) for r < rows: basicMul (helpers/mps.swift:14-47) for a block -- x rounded to f16 once, exact f16 products, f32
+ * sums -- on v_mfma_f32_16x16x32_f16; W f16 [outDim][inDim] row-major as effort_dense_gemv takes it, x f32 [rows][inDim], out f32
+ * [rows][outDim].  The weights are read once per call, whatever rows is.  inDim % 32 == 0, inDim <= 65536, 1 <= outDim <= 2^24, W below 4 GiB;
+ * anything else returns EFFORT_ERR_SHAPE (the caller falls back to effort_dense_gemv row by row).
+ * CONTRACT: row r of out depends on row r of x and on W only -- not on rows, not on the other rows, not on r: its bits are the same
+ * for every rows and every row position (the order of the sums over k is fixed).  Token columns past rows are zero operands: no x row
+ * at or beyond rows is read, no out element at or beyond rows * outDim is written.  It agrees with effort_dense_gemv to rounding of
+ * the f32 sums, not bit for bit (another order).  Uses context scratch of its own, shared with no other entry point: 64 * inDim halves
+ * for f16(x) and splits * 64 * outDim floats for the partial sums of its k split (splits <= 16, a function of the shape).  Both only
+ * grow: a call that needs more than there is synchronises the stream, frees and allocates.  The entry point is meant to be called
+ * eagerly.  A captured graph that holds it keeps the scratch addresses of its capture, so it stays valid only if no later call grows
+ * either buffer: before capturing, call it eagerly with 64 rows once for EVERY (inDim, outDim) pair the context will ever see.
+ * Up to three launches: convert, multiply, and the reduce when the shape has more than one split. */
+EFFORT_API int effort_dense_gemm_rows(effort_ctx* ctx, const void* W_f16_dev, const float* x_dev, float* out_dev, int inDim, int outDim, int rows);
+/* Block forms of the glue: per row, BIT FOR BIT what the single-token entry point writes (the same sums in the same order).
+ * effort_fetch_rows: out[r] = row ids_dev[r] of the table (effort_fetch_row).
+ * effort_add_rmsnorm_mul_rows: effort_add_rmsnorm_mul on row r of h, delta (may be NULL) and out; one norm weight vector.
+ * effort_rope_kv_rows: effort_rope_kv with row r roped at position pos0 + r; cache rows pos0 .. pos0 + rows - 1 are written, no other.
+ *   xq f32 [rows][numHeads * headDim], xk / xv f32 [rows][numHeadsKV * headDim], q_out as xq.  Head geometry as effort_rope_kv.
+ * effort_attention_rows: row r is effort_attention at position pos0 + r: it attends over cache rows 0 .. pos0 + r (causal inside the
+ *   block) and reads no cache row beyond.  A grid of (numHeads, rows) workgroups; every query reads its keys and values from the cache
+ *   again.  It needs the block's effort_rope_kv_rows to have completed: enqueue both on the context's stream.  Head geometry as
+ *   effort_attention. */
+EFFORT_API int effort_fetch_rows(effort_ctx* ctx, const void* emb_f16_dev, const uint32_t* ids_dev, float* out_dev, int n, int rows);
+EFFORT_API int effort_add_rmsnorm_mul_rows(effort_ctx* ctx, float* h_dev, const float* delta_dev, const void* w_f16_dev, float* out_dev, int n, int rows);
+EFFORT_API int effort_rope_kv_rows(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
+                        float* k_cache_dev, float* v_cache_dev, int pos0, int rows, int numHeads, int numHeadsKV, int headDim,
+                        int maxTokens, float ropeBase);
+EFFORT_API int effort_attention_rows(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev, int pos0, int rows,
+                          float* out_dev, int numHeads, int headDim, int maxTokens);
+
 /* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */
 
 /* The settings of effort_sample live in DEVICE memory (a token step is captured once into a hipGraph and graphs are kept for the

@@ -6,7 +6,9 @@ column split projected on one GPU), the one-GPU `layer_latency` (a world of one 
 decode loop on the reference's Q4 model beside the FP16 one) and `decode_mixtral` (the routed decode loop at Mixtral-8x7B shapes: dense,
 and effort with the glue kernels separate or folded; its record also goes to profiles/r07_decode_mixtral.json) and `decode_sampled` (the
 decode loop ending in the device-side top-k / top-p / temperature pick beside the greedy one, and the two closing kernels alone; its
-record also goes to profiles/r08_decode_sampled.json).
+record also goes to profiles/r08_decode_sampled.json) and `decode_prefill` (prompt ingest: the block multiply effort_dense_gemm_rows
+beside the dense GEMV on rotating matrices, and a 256-token prompt through `Decoder.prefill` beside the token-by-token loop; its
+record also goes to profiles/r09_prefill.json; asked for alone, it skips the headline job and its matrix sets).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -23,7 +25,8 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled")
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill")
+STANDALONE = ("decode_prefill",)             # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -399,6 +402,128 @@ def decode_sampled(b, res):
     del dec, model
 
 
+def decode_prefill(b, res):
+    """Prompt ingest.  Kernel legs: effort_dense_gemm_rows at rows = 1, 16, 64 beside effort_dense_gemv on the decode loop's four matrix
+    shapes -- a pass over ROTATING disjoint matrices (more than 768 MB of them per shape: nothing of a matrix is still cached when its
+    turn comes again) captured into one graph, device events around replays, best of 3 windows after a warm-up; us per call and TB/s of
+    weight bytes.  Model legs, Mistral-7B shapes, a 256-token prompt, one process: token by token through the captured dense step (how
+    a prompt is ingested without prefill: the baseline) and at 25 % effort, and `Decoder.prefill` at chunk 16 and 64 (synchronised wall
+    time, best of 3, eager launches: the host's launch work is in it); ms per prompt token each."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(77)
+
+    def us_per_call(fn, calls):
+        g._bind_stream()
+        fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            fn()
+        g._bind_stream()
+        for _ in range(3):
+            gr.replay()
+        torch.cuda.synchronize()
+        best = float("inf")
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
+        return best
+
+    kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events; TB/s = weight bytes / time"}
+    for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
+        nbytes = outD * inD * 2
+        count = max(4, -(-(768 << 20) // nbytes))
+        Ws = [(torch.randn((outD, inD), generator=gen, device=b.dev, dtype=torch.float32) * 0.02).to(torch.float16) for _ in range(count)]
+        x = torch.randn((64, inD), generator=gen, device=b.dev, dtype=torch.float32)
+        out = torch.zeros((64, outD), device=b.dev)
+
+        def gemv():
+            g._bind_stream()
+            for W in Ws:
+                g.check(lib.effort_dense_gemv(g.ctx, p(W), p(x), p(out), inD, outD), "dense_gemv")
+
+        def gemm(rows):
+            def fn():
+                g._bind_stream()
+                for W in Ws:
+                    g.check(lib.effort_dense_gemm_rows(g.ctx, p(W), p(x), p(out), inD, outD, rows), "dense_gemm_rows")
+            return fn
+        row = {"matrices": count, "weight_bytes": nbytes}
+        for name, fn in (("dense_gemv", gemv), ("gemm_rows_1", gemm(1)), ("gemm_rows_16", gemm(16)), ("gemm_rows_64", gemm(64))):
+            us = us_per_call(fn, count)
+            row[name] = {"us_per_call": round(us, 2), "TBps_of_weight_bytes": round(nbytes / us / 1e6, 3)}
+        for rows in (1, 16, 64):
+            row[f"gemm_rows_{rows}_over_gemv_time"] = round(row[f"gemm_rows_{rows}"]["us_per_call"] / row["dense_gemv"]["us_per_call"], 3)
+        kern[f"{inD}->{outD}"] = row
+        del Ws, x, out
+        torch.cuda.empty_cache()
+    out = {"kernel": kern}
+
+    nprompt = 256
+    model = Model.random(MistralConfig(), seed=1)
+    dec = Decoder(model, maxTokens=nprompt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+
+    def token_loop(**kw):
+        best = float("inf")
+        for _ in range(2):
+            _, dt, _ = dec.run(prompt, nprompt, **kw)
+            best = min(best, dt)
+        return round(best * 1e3, 4)
+
+    def prefill(chunk):
+        dec.prefill(prompt, chunk=chunk)                         # the warm call: it makes the buffers and warms the kernels; not timed
+        best = float("inf")
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dec.prefill(prompt, chunk=chunk)
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t0)
+        return round(best * 1e3 / nprompt, 4)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "prompt_tokens": nprompt,
+         "protocol": "token loop: hipGraph replay of the step, timed from the 3rd step, best of 2 runs (LM head and pick in it); prefill: eager, "
+                     "synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call (no LM head, the last layer "
+                     "stops after its cache write)"}
+    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dense=True)
+    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(effort=0.25)
+    m["prefill_chunk_16_ms_per_prompt_token"] = prefill(16)
+    m["prefill_chunk_64_ms_per_prompt_token"] = prefill(64)
+    m["prefill_chunk_16_again_ms_per_prompt_token"] = prefill(16)
+    ids, _, _ = dec.run(prompt, nprompt + 4, effort=0.25, prefill=True)
+    m["run_prefill_true_last_prefill_s"] = round(dec.last_prefill_s, 5)
+    m["run_prefill_true_picks"] = ids[nprompt - 1:]
+    base = m["token_by_token_dense_ms_per_prompt_token"]
+    for k in ("token_by_token_effort_0.25", "prefill_chunk_16", "prefill_chunk_64"):
+        m[f"dense_token_loop_over_{k}"] = round(base / m[f"{k}_ms_per_prompt_token"], 2)
+    m["prompt_512_tokens_projected_s"] = {k: round(m[f"{k}_ms_per_prompt_token"] * 512 / 1e3, 4)
+                                          for k in ("token_by_token_dense", "token_by_token_effort_0.25", "prefill_chunk_16", "prefill_chunk_64")}
+    out["model"] = m
+    res["decode_prefill"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r09_prefill.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -414,7 +539,17 @@ def layer_latency(b, res):
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
-       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled}
+       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill}
+
+
+class Light:
+    """What the STANDALONE sections read of bench.Bench: torch, the package, the device and its default context."""
+
+    def __init__(self):
+        import effort_amd
+        import torch
+        self.torch, self.ea, self.dev = torch, effort_amd, "cuda:0"
+        self.g = effort_amd.gpu()
 
 
 def main():
@@ -427,9 +562,13 @@ def main():
     args = B.parse_args(argv)
     import torch
     torch.cuda.set_device(0)
-    b = B.Bench(args)
-    b.headline()                                                  # (the sections price themselves against the headline's dispatch count)
-    res = {"what": "bench.py's auxiliary sections (tools/bench_extra.py)", "headline_us_per_call": round(b.dt / B.N_MATS * 1e6, 3), "dispatch_rows": b.D}
+    if all(name in STANDALONE for name in sections):
+        b = Light()
+        res = {"what": "bench.py's auxiliary sections (tools/bench_extra.py)"}
+    else:
+        b = B.Bench(args)
+        b.headline()                                              # (the sections price themselves against the headline's dispatch count)
+        res = {"what": "bench.py's auxiliary sections (tools/bench_extra.py)", "headline_us_per_call": round(b.dt / B.N_MATS * 1e6, 3), "dispatch_rows": b.D}
     for name in sections:
         t0 = time.perf_counter()
         try:

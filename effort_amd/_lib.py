@@ -98,6 +98,7 @@ _SIGS = {
     "effort_add_rmsnorm_mul_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "effort_rope_kv_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "effort_attention_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "effort_attention_block": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "effort_set_dense_backend": (C.c_int, [_P, C.c_int]),
     "effort_last_dispatch_count": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "effort_last_cutoff": (C.c_int, [_P, C.POINTER(C.c_float)]),

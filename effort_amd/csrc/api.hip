@@ -1133,6 +1133,16 @@ extern "C" int effort_attention_rows(effort_ctx* c, const float* q, const float*
     HIP_TRY(c, launch_attention_rows(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream));
     return EFFORT_OK;
 }
+extern "C" int effort_attention_block(effort_ctx* c, const float* q, const float* kCache, const float* vCache, int pos0, int rows, float* out,
+                                      int numHeads, int headDim, int maxTokens) {
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return fail(c, EFFORT_ERR_ARG, "attention_block: 1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (numHeads <= 0 || maxTokens > 8192 || (headDim != 64 && headDim != 128 && headDim != 256))
+        return fail(c, EFFORT_ERR_SHAPE, "attention_block: headDim 64/128/256, maxTokens <= 8192");
+    if (!c || !q || !kCache || !vCache || !out) return fail(c, EFFORT_ERR_ARG, "attention_block: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_attention_block(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream));
+    return EFFORT_OK;
+}
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {
     if (!c || !gate || !idx2 || !val2 || n < 1) return fail(c, EFFORT_ERR_ARG, "top2_softmax: bad argument");
     { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }

@@ -270,6 +270,9 @@ hipError_t launch_rope_kv_rows(const float* xq, const float* xk, const float* xv
                                uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, hipStream_t st);
 hipError_t launch_attention_rows(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
                                  uint32_t numHeads, uint32_t headDim, hipStream_t st);
+// prefill attention with the block's queries sharing each K / V tile (attention_block.hip): flash-style, f32 MFMA, headDim 64 / 128 / 256
+hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                  uint32_t numHeads, uint32_t headDim, hipStream_t st);
 
 // the sampled pick (sample.hip)
 hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,

@@ -488,7 +488,7 @@ class Decoder:
             return
         g.check(rc, "dense_gemm_rows")
 
-    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64):
+    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows"):
         """Ingest prompt tokens in bulk: fill ``kCache`` / ``vCache`` rows ``pos0 .. pos0 + T - 1`` of every layer, in blocks of at most
         ``chunk`` (<= 64) tokens that share ONE pass over each matrix, then set ``pos`` to ``pos0 + T``.  No logits, no pick: the next
         ``token_step`` (or graph replay) continues from the caches.  Eager, never captured: ``pos0`` and the block sizes are host values.
@@ -500,8 +500,14 @@ class Decoder:
         way) -> wq, wk, wv -> rope + cache write -> attention over rows 0 .. its own -> wo -> norm -> w1, w3 -> silu -> w2; the last
         layer stops after its cache write, since nothing behind it reaches a cache.
 
+        ``attention``: ``"rows"`` is effort_attention_rows (every query of a block reads its keys and values again; the token step's
+        bits); ``"block"`` puts effort_attention_block in its place, same operands -- the block's queries share each K / V tile, f32
+        MFMA with an online softmax, within the f32 bar of the same float64 value but not the same bits.  On either path the caches
+        do not depend on ``chunk``.
+
         Raises ValueError, before anything is enqueued: a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
-        them), a Mixtral model, a column-sharded decoder, ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64."""
+        them), a Mixtral model, a column-sharded decoder, ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other
+        than ``"rows"`` / ``"block"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
         T = len(ids)
@@ -515,6 +521,10 @@ class Decoder:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
+        if attention not in ("rows", "block"):
+            raise ValueError(f"Decoder.prefill: attention must be 'rows' or 'block', not {attention!r}")
+        attend, attendName = ((lib.effort_attention_rows, "attention_rows") if attention == "rows" else
+                              (lib.effort_attention_block, "attention_block"))
         g._bind_stream()
         self._prefill_buffers(chunk)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
@@ -533,8 +543,7 @@ class Decoder:
                                            cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
                 if n == len(m.layers) - 1:
                     break                                  # nothing after the last layer's cache write reaches a cache
-                ck(lib.effort_attention_rows(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim,
-                                             self.maxTokens), "attention_rows")
+                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim, self.maxTokens), attendName)
                 self._gemm_rows(self.pf_attnOutput, L.wo.core, self.pf_attnFfnOut, rows)
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 self._gemm_rows(self.pf_norm, L.w1.core, self.pf_x1, rows)
@@ -574,7 +583,8 @@ class Decoder:
         self.history.zero_()
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
-            collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64):
+            collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64,
+            prefill_attention: str = "rows"):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
@@ -584,6 +594,7 @@ class Decoder:
         and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
+        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``).
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
@@ -599,7 +610,7 @@ class Decoder:
         if skip:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            self.prefill(tokenIds[:skip], 0, prefill_chunk)
+            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention)
             torch.cuda.synchronize()
             self.last_prefill_s = time.perf_counter() - tp
         for step in range(skip, numTokens):

@@ -382,6 +382,22 @@ EFFORT_API int effort_rope_kv_rows(effort_ctx* ctx, const float* xq_dev, const f
                         int maxTokens, float ropeBase);
 EFFORT_API int effort_attention_rows(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev, int pos0, int rows,
                           float* out_dev, int numHeads, int headDim, int maxTokens);
+/* effort_attention_block: what effort_attention_rows computes -- out[r] = softmax(q[r] . K[t] / sqrt(headDim)) . V[t] over cache rows
+ * t = 0 .. pos0 + r, causal inside the block --, with the block's queries SHARING each K / V row that is fetched: a workgroup is one
+ * head and 16 queries and walks the keys in tiles of 16 with an online softmax (running max, running sum, a [16 x headDim]
+ * accumulator), both products on the f32-input MFMA (v_mfma_f32_16x16x4_f32), f32 end to end.  A fetched K / V
+ * tile serves 16 queries, so it asks for a sixteenth of effort_attention_rows's K / V bytes, and its LDS does not grow with the position.
+ * Arguments, layouts and refusals (same codes, same order, nothing enqueued) are effort_attention_rows's, one for one; eager only.
+ * BAR: every output element is within 2e-5 * max|row| of the float64 value, cosine >= 0.999999 (tests/test_gpu_attention_block.py).
+ * Its BITS DIFFER from effort_attention / effort_attention_rows: another order of the sums.
+ * ORDER OF THE SUMS: it follows the absolute position only.  Key tiles sit on multiples of 16 counted from token 0, the wave that
+ * owns a tile follows from the tile's absolute index, partial states merge in a fixed order, and a key a query may not see is
+ * selected out (never multiplied by zero), so a wholly masked tile is an exact no-op.  An output row's bits are a function of the
+ * query, its absolute position pos0 + r and cache rows 0 .. pos0 + r: not of pos0, rows or r on their own.
+ * No cache row at or past pos0 + rows and no q row at or past rows is read (they may hold NaN); nothing outside out[0 .. rows) is
+ * written.  It needs the block's effort_rope_kv_rows to have completed: enqueue both on the context's stream. */
+EFFORT_API int effort_attention_block(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev, int pos0, int rows,
+                           float* out_dev, int numHeads, int headDim, int maxTokens);
 
 /* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */
 

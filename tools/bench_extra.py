@@ -8,7 +8,9 @@ and effort with the glue kernels separate or folded; its record also goes to pro
 decode loop ending in the device-side top-k / top-p / temperature pick beside the greedy one, and the two closing kernels alone; its
 record also goes to profiles/r08_decode_sampled.json) and `decode_prefill` (prompt ingest: the block multiply effort_dense_gemm_rows
 beside the dense GEMV on rotating matrices, and a 256-token prompt through `Decoder.prefill` beside the token-by-token loop; its
-record also goes to profiles/r09_prefill.json; asked for alone, it skips the headline job and its matrix sets).
+record also goes to profiles/r09_prefill.json; asked for alone, it skips the headline job and its matrix sets) and `prefill_attention`
+(effort_attention_rows beside effort_attention_block on rotating caches, and 256- and 2048-token prompts through `Decoder.prefill` on
+both attention paths; its record also goes to profiles/r10_prefill_attention.json; standalone like `decode_prefill`).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -25,8 +27,8 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill")
-STANDALONE = ("decode_prefill",)             # sections that read neither the headline nor the matrix sets of bench.Bench
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention")
+STANDALONE = ("decode_prefill", "prefill_attention")             # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -524,6 +526,110 @@ def decode_prefill(b, res):
     del dec, model
 
 
+def prefill_attention(b, res):
+    """Prefill attention: effort_attention_rows (every query of a block reads K / V again) beside effort_attention_block (the block's
+    queries share each K / V tile), one process.  Kernel legs, decode_prefill's protocol: 32 heads, headDim 128, maxTokens 8192, a pass
+    over four ROTATING cache pairs (1 GB: a pair is 268 MB, nothing of it is still cached when its turn comes again) captured into one
+    graph, device events, best of 3 windows after a warm-up; us per call and the K / V bytes each kernel asks for.  Model legs,
+    Mistral-7B shapes: `Decoder.prefill` over a 256-token and a 2048-token prompt at chunk 64 on both paths (synchronised wall time,
+    best of 3 after a warm call); ms per prompt token."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(78)
+    heads, hd, maxTokens, pairs = 32, 128, 8192, 4
+
+    def us_per_call(fn, calls):
+        g._bind_stream()
+        fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            fn()
+        g._bind_stream()
+        for _ in range(3):
+            gr.replay()
+        torch.cuda.synchronize()
+        best = float("inf")
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
+        return best
+
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    caches = [(rnd(maxTokens, heads, hd), rnd(maxTokens, heads, hd)) for _ in range(pairs)]
+    q, out = rnd(64, heads * hd), torch.zeros((64, heads * hd), device=b.dev)
+    rowBytes = heads * hd * 4 * 2                                                # K and V of one token, every head
+
+    def leg(entry, what, pos0, rows):
+        def fn():
+            g._bind_stream()
+            for kc, vc in caches:
+                g.check(entry(g.ctx, p(q), p(kc), p(vc), pos0, rows, p(out), heads, hd, maxTokens), what)
+        return fn
+    kern = {"protocol": "one pass over 4 rotating cache pairs per graph, 4 replays per window, best of 3 windows, device events; "
+                        "kv_bytes = cache rows each kernel asks for x 32 KB (K + V of a token, 32 heads)",
+            "heads": heads, "headDim": hd, "maxTokens": maxTokens}
+    for pos0, rows in ((0, 64), (192, 64), (960, 64), (4032, 64), (8128, 64), (4032, 16)):
+        asked = {"attention_rows": sum(pos0 + r + 1 for r in range(rows)),
+                 "attention_block": sum(min(pos0 + rows, ((pos0 + min(16 * t + 15, rows - 1)) // 16 + 1) * 16) for t in range((rows + 15) // 16))}
+        row = {}
+        for name, entry in (("attention_rows", lib.effort_attention_rows), ("attention_block", lib.effort_attention_block)):
+            us = us_per_call(leg(entry, name, pos0, rows), pairs)
+            row[name] = {"us_per_call": round(us, 2), "kv_bytes": asked[name] * rowBytes, "TBps_of_kv_bytes": round(asked[name] * rowBytes / us / 1e6, 3)}
+        row["rows_over_block_time"] = round(row["attention_rows"]["us_per_call"] / row["attention_block"]["us_per_call"], 2)
+        row["rows_over_block_bytes"] = round(asked["attention_rows"] / asked["attention_block"], 2)
+        kern[f"pos0_{pos0}_rows_{rows}"] = row
+    del caches, q, out
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "chunk": 64,
+         "protocol": "eager, synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call"}
+    for nprompt in (256, 2048):
+        dec = Decoder(model, maxTokens=nprompt + 8)
+        prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+        for attention in ("rows", "block", "rows"):                              # (the rows path twice: its own run-to-run spread)
+            dec.prefill(prompt, chunk=64, attention=attention)
+            best = float("inf")
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                dec.prefill(prompt, chunk=64, attention=attention)
+                torch.cuda.synchronize()
+                best = min(best, time.perf_counter() - t0)
+            key = f"prompt_{nprompt}_{attention}_ms_per_prompt_token"
+            m[key + "_again" if key in m else key] = round(best * 1e3 / nprompt, 4)
+        m[f"prompt_{nprompt}_rows_over_block"] = round(m[f"prompt_{nprompt}_rows_ms_per_prompt_token"] / m[f"prompt_{nprompt}_block_ms_per_prompt_token"], 3)
+        del dec
+        torch.cuda.empty_cache()
+    res_out["model"] = m
+    res_out["acceptance"] = {
+        "kernel_pos0_4032_rows_64_block_faster_by_more_than_5_percent": kern["pos0_4032_rows_64"]["rows_over_block_time"] > 1.05,
+        "model_256_block_no_slower_than_rows_beyond_5_percent": m["prompt_256_rows_over_block"] >= 1.0 / 1.05}
+    res["prefill_attention"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r10_prefill_attention.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -539,7 +645,7 @@ def layer_latency(b, res):
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
-       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill}
+       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention}
 
 
 class Light:

@@ -125,6 +125,19 @@ static int fail(effort_ctx* c, int code, const char* what, hipError_t e = hipSuc
         if (e_ != hipSuccess) return fail((ctx), EFFORT_ERR_HIP, #call, e_); \
     } while (0)
 
+// Context scratch that only grows: `have` elements at `buf`.  An adequate buffer is left untouched (its address may sit in a captured
+// graph); otherwise the stream is synchronised (nothing in flight reads the old one), the old one freed and `want` >= need elements
+// allocated.  A failed allocation leaves buf null and have 0.
+template <typename T>
+static int grow_scratch(effort_ctx* c, T*& buf, size_t& have, size_t need, size_t want) {
+    if (need <= have) return EFFORT_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipFree(buf); buf = nullptr; have = 0;
+    HIP_TRY(c, hipMalloc(&buf, want * sizeof(T)));
+    have = want;
+    return EFFORT_OK;
+}
+
 // RCCL is bound at RUN time, when the first communicator is asked for: a single-GPU host needs no librccl to load this library,
 // and a process that has one mapped already (PyTorch-ROCm brings its own copy) gets THAT one -- dlopen by soname returns the copy
 // already in the process -- so two RCCLs never meet in one address space; a plain C / Swift host gets the system ROCm's.
@@ -941,12 +954,7 @@ extern "C" int effort_dense_gemv(effort_ctx* c, const void* W, const float* v, f
         rocblas_set_stream(c->blas, c->stream);
         rocblas_set_pointer_mode(c->blas, rocblas_pointer_mode_host);
     }
-    if ((size_t)inDim > c->vhalfElems) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_vhalf); c->d_vhalf = nullptr; c->vhalfElems = 0;
-        HIP_TRY(c, hipMalloc(&c->d_vhalf, (size_t)inDim * 2));
-        c->vhalfElems = inDim;
-    }
+    { const int grc = grow_scratch(c, c->d_vhalf, c->vhalfElems, (size_t)inDim, (size_t)inDim); if (grc != EFFORT_OK) return grc; }
     HIP_TRY(c, launch_f32_to_f16(v, c->d_vhalf, inDim, c->stream));                  // v.asFloat16(), mps.swift:19
     // W is [outDim][inDim] row-major == column-major inDim x outDim with lda = inDim: y = A^T x
     const float alpha = 1.0f, beta = 0.0f;
@@ -978,12 +986,7 @@ extern "C" int effort_convert_fp16_pitched(effort_ctx* c, const void* W, int out
     const int pitch = rowPitchBytes ? rowPitchBytes : outDim / 16 * 2;
     if (pitch < outDim / 16 * 2 || pitch % 8) return fail(c, EFFORT_ERR_CONVERT, "convert_fp16: row pitch must be a multiple of 8 bytes >= 2*cols");   // (the stats pass loads 8 bytes at a time)
     const size_t elems = (size_t)outDim * inDim;
-    if (elems > c->convElems) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_convVals); c->d_convVals = nullptr; c->convElems = 0;
-        HIP_TRY(c, hipMalloc(&c->d_convVals, elems * 2));
-        c->convElems = elems;
-    }
+    { const int grc = grow_scratch(c, c->d_convVals, c->convElems, elems, elems); if (grc != EFFORT_OK) return grc; }
     HIP_TRY(c, launch_convert_fp16(static_cast<const uint16_t*>(W), outDim, inDim, static_cast<uint16_t*>(buckets), (uint32_t)pitch / 2u,
                                    static_cast<uint16_t*>(stats), static_cast<uint16_t*>(probes), c->d_convVals, c->d_status, c->stream));
     return EFFORT_OK;
@@ -1068,8 +1071,9 @@ extern "C" int effort_fetch_row(effort_ctx* c, const void* emb, const uint32_t* 
     HIP_TRY(c, launch_fetch_row(static_cast<const uint16_t*>(emb), id, out, (uint32_t)n, c->stream));
     return EFFORT_OK;
 }
-// ---- prompt prefill (prefill.hip): a block of tokens per call.  pos0 and rows are HOST values (prefill is eager, never captured), so
-// every refusal is a return code with nothing enqueued; the values are judged before the pointers, the lanes are joined before the launch.
+// ---- prompt prefill (the block multiply in prefill.hip, the block glue in decode.hip): a block of tokens per call.  pos0 and rows are
+// HOST values (prefill is eager, never captured), so every refusal is a return code with nothing enqueued; the values are judged before
+// the pointers, the lanes are joined before the launch.
 static_assert(EFFORT_PREFILL_MAX_ROWS == 64, "prefill.hip: kPrefillMaxRows, four token tiles of 16");
 static bool prefill_rows_ok(int rows) { return rows >= 1 && rows <= EFFORT_PREFILL_MAX_ROWS; }
 extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float* x, float* out, int inDim, int outDim, int rows) {
@@ -1078,20 +1082,12 @@ extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float*
         return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, W below 4 GiB");
     if (!c || !W || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows: null argument");
     { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
-    if ((size_t)rows * inDim > c->xhRowsElems) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_xhRows); c->d_xhRows = nullptr; c->xhRowsElems = 0;
-        const size_t want = (size_t)EFFORT_PREFILL_MAX_ROWS * inDim;                 // (a block's worth: the next, longer block does not allocate again)
-        HIP_TRY(c, hipMalloc(&c->d_xhRows, want * 2));
-        c->xhRowsElems = want;
-    }
-    if (dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows) > c->gemmPartFloats) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_gemmPart); c->d_gemmPart = nullptr; c->gemmPartFloats = 0;
-        const size_t want = dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS);
-        HIP_TRY(c, hipMalloc(&c->d_gemmPart, want * sizeof(float)));
-        c->gemmPartFloats = want;
-    }
+    // (a block's worth of both: the next, longer block does not allocate again)
+    int grc = grow_scratch(c, c->d_xhRows, c->xhRowsElems, (size_t)rows * inDim, (size_t)EFFORT_PREFILL_MAX_ROWS * inDim);
+    if (grc == EFFORT_OK)
+        grc = grow_scratch(c, c->d_gemmPart, c->gemmPartFloats, dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows),
+                           dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS));
+    if (grc != EFFORT_OK) return grc;
     HIP_TRY(c, launch_dense_gemm_rows(static_cast<const uint16_t*>(W), x, c->d_xhRows, c->d_gemmPart, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows,
                                       c->stream));
     return EFFORT_OK;
@@ -1123,25 +1119,27 @@ extern "C" int effort_rope_kv_rows(effort_ctx* c, const float* xq, const float* 
     HIP_TRY(c, launch_rope_kv_rows(xq, xk, xv, qOut, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, numHeads, numHeadsKV, headDim, ropeBase, c->stream));
     return EFFORT_OK;
 }
+// The two prefill attentions take the same arguments and refuse the same ones; `name` heads the messages.
+static int prefill_attention(effort_ctx* c, const char* name, decltype(&launch_attention_rows) launch, const float* q, const float* kCache,
+                             const float* vCache, int pos0, int rows, float* out, int numHeads, int headDim, int maxTokens) {
+    char what[96];
+    auto refuse = [&](int code, const char* why) { snprintf(what, sizeof(what), "%s: %s", name, why); return fail(c, code, what); };
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return refuse(EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (numHeads <= 0 || maxTokens > 8192 || (headDim != 64 && headDim != 128 && headDim != 256))
+        return refuse(EFFORT_ERR_SHAPE, "headDim 64/128/256, maxTokens <= 8192");
+    if (!c || !q || !kCache || !vCache || !out) return refuse(EFFORT_ERR_ARG, "null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    const hipError_t e = launch(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream);
+    if (e != hipSuccess) return fail(c, EFFORT_ERR_HIP, name, e);
+    return EFFORT_OK;
+}
 extern "C" int effort_attention_rows(effort_ctx* c, const float* q, const float* kCache, const float* vCache, int pos0, int rows, float* out,
                                      int numHeads, int headDim, int maxTokens) {
-    if (!prefill_range_ok(pos0, rows, maxTokens)) return fail(c, EFFORT_ERR_ARG, "attention_rows: 1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
-    if (numHeads <= 0 || maxTokens > 8192 || (headDim != 64 && headDim != 128 && headDim != 256))
-        return fail(c, EFFORT_ERR_SHAPE, "attention_rows: headDim 64/128/256, maxTokens <= 8192");
-    if (!c || !q || !kCache || !vCache || !out) return fail(c, EFFORT_ERR_ARG, "attention_rows: null argument");
-    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
-    HIP_TRY(c, launch_attention_rows(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream));
-    return EFFORT_OK;
+    return prefill_attention(c, "attention_rows", launch_attention_rows, q, kCache, vCache, pos0, rows, out, numHeads, headDim, maxTokens);
 }
 extern "C" int effort_attention_block(effort_ctx* c, const float* q, const float* kCache, const float* vCache, int pos0, int rows, float* out,
                                       int numHeads, int headDim, int maxTokens) {
-    if (!prefill_range_ok(pos0, rows, maxTokens)) return fail(c, EFFORT_ERR_ARG, "attention_block: 1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
-    if (numHeads <= 0 || maxTokens > 8192 || (headDim != 64 && headDim != 128 && headDim != 256))
-        return fail(c, EFFORT_ERR_SHAPE, "attention_block: headDim 64/128/256, maxTokens <= 8192");
-    if (!c || !q || !kCache || !vCache || !out) return fail(c, EFFORT_ERR_ARG, "attention_block: null argument");
-    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
-    HIP_TRY(c, launch_attention_block(q, kCache, vCache, (uint32_t)pos0, (uint32_t)rows, out, numHeads, headDim, c->stream));
-    return EFFORT_OK;
+    return prefill_attention(c, "attention_block", launch_attention_block, q, kCache, vCache, pos0, rows, out, numHeads, headDim, maxTokens);
 }
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {
     if (!c || !gate || !idx2 || !val2 || n < 1) return fail(c, EFFORT_ERR_ARG, "top2_softmax: bad argument");

@@ -12,6 +12,8 @@
 //                    bit for bit what add_rmsnorm_mul -> dense_gemv_kernel<1, 0> -> top2_softmax write in a row
 //   mix2_add         h += f0 * val[0] + f1 * val[1]: mix2 and the residual add the next norm would have done (runNetwork.swift:190-199)
 //   argmax           greedy pick of the next token (the reference takes mpsTopK[0], helpers/mps.swift:52-84), pos += 1
+// add_rmsnorm_mul, rope_kv, attention and fetch_row each have a block form (*_rows) over `rows` tokens for prompt prefill: one workgroup
+// (fetch: one grid row) per token, running the SAME body as the token form -- per token it writes the token form's bits.
 #include "effort_internal.h"
 
 namespace effort {
@@ -38,9 +40,9 @@ __device__ __forceinline__ float block_max(float x, float* red) {
     return s;
 }
 
-__global__ __launch_bounds__(1024) void add_rmsnorm_mul_kernel(float* __restrict__ h, const float* __restrict__ delta,
-                                                               const uint16_t* __restrict__ w, float* __restrict__ out, uint32_t n) {
-    __shared__ float red[17];
+// One row of n elements, block = 1024; delta may be null (nothing is added, h is not written).
+__device__ __forceinline__ void add_rmsnorm_mul_row(float* __restrict__ h, const float* __restrict__ delta, const uint16_t* __restrict__ w,
+                                                    float* __restrict__ out, uint32_t n, float* red /* [17] */) {
     // One memory round trip: every load (h, delta, the norm weights) is issued before anything is used, the updated state
     // stays in registers for the second half (n <= 4 * 1024 elements per register slot; a longer state takes the loop
     // below).  This kernel sits on the decode loop's dependent chain twice per layer.
@@ -78,39 +80,67 @@ __global__ __launch_bounds__(1024) void add_rmsnorm_mul_kernel(float* __restrict
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = (h[i] * inv) * half_bits_to_float(w[i]);
 }
 
-// grid = numHeads, block = headDim.  freq_j = base^(-2j/headDim) (createFreqsCis2, model.swift:693-717: logspace with
-// base 1e-6 <=> theta 1e6), rotate_half convention of rope_mx.
-__global__ void rope_kv_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
-                               float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
-                               const uint32_t* __restrict__ posPtr, uint32_t numHeads, uint32_t kvRepeats, float logBase,
-                               uint32_t maxTokens, int* __restrict__ status) {
-    const uint32_t head = blockIdx.x, d = threadIdx.x, headDim = blockDim.x, half = headDim / 2, pos = posPtr[0];
-    if (pos >= maxTokens) {                            // past the cache: nothing is written, the context's status word says so
-        if (head == 0 && d == 0) atomicOr(status, 1);
-        return;
-    }
+__global__ __launch_bounds__(1024) void add_rmsnorm_mul_kernel(float* __restrict__ h, const float* __restrict__ delta,
+                                                               const uint16_t* __restrict__ w, float* __restrict__ out, uint32_t n) {
+    __shared__ float red[17];
+    add_rmsnorm_mul_row(h, delta, w, out, n, red);
+}
+// grid = rows, block = 1024: row blockIdx.x of h, delta and out
+__global__ __launch_bounds__(1024) void add_rmsnorm_mul_rows_kernel(float* __restrict__ h, const float* __restrict__ delta,
+                                                                    const uint16_t* __restrict__ w, float* __restrict__ out, uint32_t n) {
+    __shared__ float red[17];
+    const size_t row = (size_t)blockIdx.x * n;
+    add_rmsnorm_mul_row(h + row, delta ? delta + row : nullptr, w, out + row, n, red);
+}
+
+// One head of one token at position pos, block = headDim; q, k, v and qOut point at this head's (k, v: its kv head's) headDim values.
+// freq_j = base^(-2j/headDim) (createFreqsCis2, model.swift:693-717: logspace with base 1e-6 <=> theta 1e6), rotate_half
+// convention of rope_mx.
+__device__ __forceinline__ void rope_kv_row(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                            float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
+                                            uint32_t pos, uint32_t head, uint32_t numHeads, float logBase) {
+    const uint32_t d = threadIdx.x, headDim = blockDim.x, half = headDim / 2;
     const uint32_t j = d % half;
     const float freq = (float)exp((double)logBase * (-(double)j / (double)half));          // Float(freq), model.swift:707
     const float angle = (float)pos * freq;
     const float c = cosf(angle), s = sinf(angle);
-    const float* q = xq + head * headDim;
-    const float* k = xk + (head / kvRepeats) * headDim;                                    // repeat4x32: kv head y feeds heads 4y..4y+3
     const float qr = d < half ? q[d] * c - q[d + half] * s : q[d] * c + q[d - half] * s;
     const float kr = d < half ? k[d] * c - k[d + half] * s : k[d] * c + k[d - half] * s;
     const size_t slot = ((size_t)pos * numHeads + head) * headDim + d;
-    qOut[head * headDim + d] = qr;
+    qOut[d] = qr;
     kCache[slot] = kr;
-    vCache[slot] = xv[(head / kvRepeats) * headDim + d];
+    vCache[slot] = v[d];
 }
 
-// grid = numHeads, block = 256.  Tokens 0..pos.  exp(x - max) / sum exp(x - max) == the reference's exp(x) / sum exp(x).
-__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ q, const float* __restrict__ kCache,
-                                                        const float* __restrict__ vCache, const uint32_t* __restrict__ posPtr,
-                                                        float* __restrict__ out, uint32_t numHeads, uint32_t headDim, uint32_t maxTokens) {
-    extern __shared__ float sc[];                      // [maxTokens] scores, then probabilities
-    __shared__ float red[17];
-    const uint32_t head = blockIdx.x, tid = threadIdx.x, nTok = min(posPtr[0] + 1u, maxTokens);
-    const float* qh = q + head * headDim;
+// grid = numHeads, block = headDim
+__global__ void rope_kv_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
+                               float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
+                               const uint32_t* __restrict__ posPtr, uint32_t numHeads, uint32_t kvRepeats, float logBase,
+                               uint32_t maxTokens, int* __restrict__ status) {
+    const uint32_t head = blockIdx.x, headDim = blockDim.x, pos = posPtr[0];
+    if (pos >= maxTokens) {                            // past the cache: nothing is written, the context's status word says so
+        if (head == 0 && threadIdx.x == 0) atomicOr(status, 1);
+        return;
+    }
+    const uint32_t kvOff = (head / kvRepeats) * headDim;                                   // repeat4x32: kv head y feeds heads 4y..4y+3
+    rope_kv_row(xq + head * headDim, xk + kvOff, xv + kvOff, qOut + head * headDim, kCache, vCache, pos, head, numHeads, logBase);
+}
+// grid = (numHeads, rows), block = headDim: row blockIdx.y at position pos0 + blockIdx.y (no guard: the host checked the range)
+__global__ void rope_kv_rows_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
+                                    float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
+                                    uint32_t pos0, uint32_t numHeads, uint32_t kvRepeats, float logBase) {
+    const uint32_t head = blockIdx.x, r = blockIdx.y, headDim = blockDim.x;
+    const size_t qOff = (size_t)r * numHeads * headDim + head * headDim;
+    const size_t kvOff = (size_t)r * (numHeads / kvRepeats) * headDim + (head / kvRepeats) * headDim;
+    rope_kv_row(xq + qOff, xk + kvOff, xv + kvOff, qOut + qOff, kCache, vCache, pos0 + r, head, numHeads, logBase);
+}
+
+// One head of one query over tokens 0 .. nTok - 1, block = 256; qh points at this head's query, out at the token's output row.
+// exp(x - max) / sum exp(x - max) == the reference's exp(x) / sum exp(x).
+__device__ __forceinline__ void attention_row(const float* __restrict__ qh, const float* __restrict__ kCache, const float* __restrict__ vCache,
+                                              uint32_t nTok, float* __restrict__ out, uint32_t head, uint32_t numHeads, uint32_t headDim,
+                                              float* sc /* [nTok] scores, then probabilities */, float* red /* [17] */, float* part /* [256] */) {
+    const uint32_t tid = threadIdx.x;
     const float scale = 1.0f / sqrtf((float)headDim);
     const int lane = tid & 63, wave = tid >> 6;
     // one wave per token: lanes stride the head dimension
@@ -131,7 +161,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     sum = block_sum(sum, red);
     const float inv = 1.0f / sum;
     // sumScores32: out[head][d] = sum_t p_t * v[t][head][d]; threads = (token phase, d)
-    __shared__ float part[256];
     const uint32_t d = tid % headDim, ph = tid / headDim, nph = 256 / headDim;
     float acc = 0.0f;
     if (ph < nph)
@@ -143,6 +172,29 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         for (uint32_t p = 0; p < nph; p++) s2 += part[p * headDim + tid];
         out[head * headDim + tid] = s2 * inv;
     }
+}
+
+// grid = numHeads, block = 256.  Tokens 0..pos.
+__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ q, const float* __restrict__ kCache,
+                                                        const float* __restrict__ vCache, const uint32_t* __restrict__ posPtr,
+                                                        float* __restrict__ out, uint32_t numHeads, uint32_t headDim, uint32_t maxTokens) {
+    extern __shared__ float sc[];                      // [maxTokens] scores, then probabilities
+    __shared__ float red[17];
+    __shared__ float part[256];
+    const uint32_t head = blockIdx.x, nTok = min(posPtr[0] + 1u, maxTokens);
+    attention_row(q + head * headDim, kCache, vCache, nTok, out, head, numHeads, headDim, sc, red, part);
+}
+// grid = (numHeads, rows), block = 256: query row blockIdx.y over tokens 0 .. pos0 + blockIdx.y.  Every query of the block reads its
+// keys and values from the cache again (no sharing among the block's queries).
+__global__ __launch_bounds__(256) void attention_rows_kernel(const float* __restrict__ q, const float* __restrict__ kCache,
+                                                             const float* __restrict__ vCache, uint32_t pos0, float* __restrict__ out,
+                                                             uint32_t numHeads, uint32_t headDim) {
+    extern __shared__ float sc[];                      // [pos0 + rows] scores, then probabilities
+    __shared__ float red[17];
+    __shared__ float part[256];
+    const uint32_t head = blockIdx.x, r = blockIdx.y;
+    const size_t row = (size_t)r * numHeads * headDim;
+    attention_row(q + row + head * headDim, kCache, vCache, pos0 + r + 1u, out + row, head, numHeads, headDim, sc, red, part);
 }
 
 // rope_kv + attention in ONE launch (one workgroup per query head): the head ropes its q and its kv head's k, stores k / v
@@ -277,9 +329,17 @@ __global__ void silu_mul_kernel(const float* __restrict__ x1, const float* __res
     if (i < n) out[i] = x3[i] * x1[i] / (1.0f + expf(-x1[i]));
 }
 
-__global__ void fetch_row_kernel(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ idPtr, float* __restrict__ out, uint32_t n) {
+// out[i] = table row idPtr[0], element i
+__device__ __forceinline__ void fetch_row_elem(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ idPtr, float* __restrict__ out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = half_bits_to_float(emb[(size_t)idPtr[0] * n + i]);
+}
+__global__ void fetch_row_kernel(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ idPtr, float* __restrict__ out, uint32_t n) {
+    fetch_row_elem(emb, idPtr, out, n);
+}
+// grid = (n / 256, rows): row ids[blockIdx.y] into row blockIdx.y of out
+__global__ void fetch_rows_kernel(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ ids, float* __restrict__ out, uint32_t n) {
+    fetch_row_elem(emb, ids + blockIdx.y, out + (size_t)blockIdx.y * n, n);
 }
 
 // one workgroup: greedy next token = index of the largest logit (lowest index on ties); advances the position
@@ -465,6 +525,10 @@ hipError_t launch_add_rmsnorm_mul(float* h, const float* delta, const uint16_t* 
     hipLaunchKernelGGL(add_rmsnorm_mul_kernel, dim3(1), dim3(1024), 0, st, h, delta, w, out, n);
     return hipGetLastError();
 }
+hipError_t launch_add_rmsnorm_mul_rows(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(add_rmsnorm_mul_rows_kernel, dim3(rows), dim3(1024), 0, st, h, delta, w, out, n);
+    return hipGetLastError();
+}
 hipError_t launch_rope_kv(const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache,
                           const uint32_t* pos, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, uint32_t maxTokens,
                           int* status, hipStream_t st) {
@@ -472,9 +536,21 @@ hipError_t launch_rope_kv(const float* xq, const float* xk, const float* xv, flo
                        numHeads / numHeadsKV, logf(ropeBase), maxTokens, status);
     return hipGetLastError();
 }
+hipError_t launch_rope_kv_rows(const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache, uint32_t pos0,
+                               uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, hipStream_t st) {
+    hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(numHeads, rows), dim3(headDim), 0, st, xq, xk, xv, qOut, kCache, vCache, pos0, numHeads,
+                       numHeads / numHeadsKV, logf(ropeBase));
+    return hipGetLastError();
+}
 hipError_t launch_attention(const float* q, const float* kCache, const float* vCache, const uint32_t* pos, float* out,
                             uint32_t numHeads, uint32_t headDim, uint32_t maxTokens, hipStream_t st) {
     hipLaunchKernelGGL(attention_kernel, dim3(numHeads), dim3(256), maxTokens * sizeof(float), st, q, kCache, vCache, pos, out, numHeads, headDim, maxTokens);
+    return hipGetLastError();
+}
+hipError_t launch_attention_rows(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                 uint32_t numHeads, uint32_t headDim, hipStream_t st) {
+    hipLaunchKernelGGL(attention_rows_kernel, dim3(numHeads, rows), dim3(256), (pos0 + rows) * sizeof(float), st, q, kCache, vCache, pos0, out,
+                       numHeads, headDim);
     return hipGetLastError();
 }
 hipError_t launch_rope_attention(const float* xq, const float* xk, const float* xv, float* kCache, float* vCache, const uint32_t* pos,
@@ -490,6 +566,10 @@ hipError_t launch_silu_mul(const float* x1, const float* x3, float* out, uint32_
 }
 hipError_t launch_fetch_row(const uint16_t* emb, const uint32_t* id, float* out, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(fetch_row_kernel, dim3((n + 255) / 256), dim3(256), 0, st, emb, id, out, n);
+    return hipGetLastError();
+}
+hipError_t launch_fetch_rows(const uint16_t* emb, const uint32_t* ids, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(fetch_rows_kernel, dim3((n + 255) / 256, rows), dim3(256), 0, st, emb, ids, out, n);
     return hipGetLastError();
 }
 hipError_t launch_argmax(const float* logits, uint32_t n, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,

@@ -5,9 +5,6 @@
 //   dense_gemm_rows   out[r] = W * f16(x[r]) for rows r of a block: basicMul's arithmetic (helpers/mps.swift:14-47: x rounded to f16
 //                     once, exact f16 products, f32 sums) on v_mfma_f32_16x16x32_f16.  An MFMA tile is 16 rows of W (A operand) by 16
 //                     tokens (B operand); up to four token tiles share every weight fragment.
-//   *_rows            block forms of the glue (decode.hip): fetch_row, add_rmsnorm_mul, rope_kv, attention, one workgroup (or one
-//                     grid row) per token of the block, the SAME sums in the same order -- per token they write the bits of the
-//                     single-token kernels, which are pinned to float64 references (tests/test_gpu_glue.py).
 //
 // The block multiply.  The weight stream is what it is bound by, and a lane's A fragment is 16 contiguous bytes of a weight row, so
 // weights go from global memory straight into the MFMA operand -- no LDS.  K is walked in stages of kPfStage = 256 elements; inside
@@ -199,161 +196,6 @@ hipError_t launch_dense_gemm_rows(const uint16_t* W, const float* x, uint16_t* x
     if (e != hipSuccess || sp.splits == 1u) return e;
     const uint32_t no = rows * outDim;
     hipLaunchKernelGGL(reduce_splits_kernel, dim3((no + 255u) / 256u), dim3(256), 0, st, part, out, no, sp.splits);
-    return hipGetLastError();
-}
-
-// ---- block forms of the glue -----------------------------------------------------------------------------------------------------
-// The sums of decode.hip, restated: block_sum / block_max (DPP scan inside a wave, then the waves' words in ascending order),
-// add_rmsnorm_mul_kernel's thread-strided squares, attention_kernel's wave-per-token dot with the xor butterfly, its softmax and
-// its phase sums.  Row r of a block is one workgroup (fetch: one grid row) running that code on its own slice of the operands.
-__device__ __forceinline__ float pf_block_sum(float x, float* red /* [17] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    x = wave_sum_f32(x);
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    float s = 0.0f;
-    for (int w = 0; w < nw; w++) s += red[w];
-    return s;
-}
-__device__ __forceinline__ float pf_block_max(float x, float* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    x = wave_max_f32(x);
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < nw; w++) s = fmaxf(s, red[w]);
-    return s;
-}
-
-// grid = (n / 256, rows)
-__global__ void fetch_rows_kernel(const uint16_t* __restrict__ emb, const uint32_t* __restrict__ ids, float* __restrict__ out, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-    if (i < n) out[(size_t)r * n + i] = half_bits_to_float(emb[(size_t)ids[r] * n + i]);
-}
-
-// grid = rows, block = 1024: add_rmsnorm_mul_kernel on row blockIdx.x of h, delta and out
-__global__ __launch_bounds__(1024) void add_rmsnorm_mul_rows_kernel(float* __restrict__ hAll, const float* __restrict__ deltaAll,
-                                                                    const uint16_t* __restrict__ w, float* __restrict__ outAll, uint32_t n) {
-    __shared__ float red[17];
-    float* h = hAll + (size_t)blockIdx.x * n;
-    const float* delta = deltaAll ? deltaAll + (size_t)blockIdx.x * n : nullptr;
-    float* out = outAll + (size_t)blockIdx.x * n;
-    constexpr int K = 4;
-    if (n <= K * 1024u) {
-        float x[K], d[K], wf[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const uint32_t i = min(k * 1024u + threadIdx.x, n - 1u);
-            x[k] = h[i];
-            d[k] = delta ? delta[i] : 0.0f;
-            wf[k] = half_bits_to_float(w[i]);
-        }
-        float ss = 0.0f;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const bool live = k * 1024u + threadIdx.x < n;
-            x[k] += d[k];
-            if (live && delta) h[k * 1024u + threadIdx.x] = x[k];
-            ss += live ? x[k] * x[k] : 0.0f;
-        }
-        const float inv = 1.0f / sqrtf(pf_block_sum(ss, red) / (float)n + 1e-5f);
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            if (k * 1024u + threadIdx.x < n) out[k * 1024u + threadIdx.x] = (x[k] * inv) * wf[k];
-        return;
-    }
-    float ss = 0.0f;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        float x = h[i];
-        if (delta) { x += delta[i]; h[i] = x; }
-        ss += x * x;
-    }
-    const float inv = 1.0f / sqrtf(pf_block_sum(ss, red) / (float)n + 1e-5f);
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = (h[i] * inv) * half_bits_to_float(w[i]);
-}
-
-// grid = (numHeads, rows), block = headDim: rope_kv_kernel on row blockIdx.y at position pos0 + blockIdx.y (the host checked the range)
-__global__ void rope_kv_rows_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
-                                    float* __restrict__ qOut, float* __restrict__ kCache, float* __restrict__ vCache,
-                                    uint32_t pos0, uint32_t numHeads, uint32_t kvRepeats, float logBase) {
-    const uint32_t head = blockIdx.x, r = blockIdx.y, d = threadIdx.x, headDim = blockDim.x, half = headDim / 2, pos = pos0 + r;
-    const uint32_t j = d % half;
-    const float freq = (float)exp((double)logBase * (-(double)j / (double)half));
-    const float angle = (float)pos * freq;
-    const float c = cosf(angle), s = sinf(angle);
-    const uint32_t kvDim = (numHeads / kvRepeats) * headDim;
-    const float* q = xq + (size_t)r * numHeads * headDim + head * headDim;
-    const float* k = xk + (size_t)r * kvDim + (head / kvRepeats) * headDim;
-    const float qr = d < half ? q[d] * c - q[d + half] * s : q[d] * c + q[d - half] * s;
-    const float kr = d < half ? k[d] * c - k[d + half] * s : k[d] * c + k[d - half] * s;
-    const size_t slot = ((size_t)pos * numHeads + head) * headDim + d;
-    qOut[(size_t)r * numHeads * headDim + head * headDim + d] = qr;
-    kCache[slot] = kr;
-    vCache[slot] = xv[(size_t)r * kvDim + (head / kvRepeats) * headDim + d];
-}
-
-// grid = (numHeads, rows), block = 256: attention_kernel on query row blockIdx.y over tokens 0 .. pos0 + blockIdx.y.  Every query
-// of the block reads its keys and values from the cache again (no sharing among the block's queries).
-__global__ __launch_bounds__(256) void attention_rows_kernel(const float* __restrict__ qAll, const float* __restrict__ kCache,
-                                                             const float* __restrict__ vCache, uint32_t pos0, float* __restrict__ outAll,
-                                                             uint32_t numHeads, uint32_t headDim) {
-    extern __shared__ float sc[];                      // [pos0 + rows] scores, then probabilities
-    __shared__ float red[17];
-    const uint32_t head = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, nTok = pos0 + r + 1u;
-    const float* qh = qAll + (size_t)r * numHeads * headDim + head * headDim;
-    float* out = outAll + (size_t)r * numHeads * headDim;
-    const float scale = 1.0f / sqrtf((float)headDim);
-    const int lane = tid & 63, wave = tid >> 6;
-    for (uint32_t t = wave; t < nTok; t += 4) {
-        const float* kh = kCache + ((size_t)t * numHeads + head) * headDim;
-        float dot = 0.0f;
-        for (uint32_t d = lane; d < headDim; d += 64) dot += qh[d] * kh[d];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) dot += __shfl_xor(dot, off);
-        if (lane == 0) sc[t] = dot * scale;
-    }
-    __syncthreads();
-    float m = -INFINITY;
-    for (uint32_t t = tid; t < nTok; t += 256) m = fmaxf(m, sc[t]);
-    m = pf_block_max(m, red);
-    float sum = 0.0f;
-    for (uint32_t t = tid; t < nTok; t += 256) { const float e = expf(sc[t] - m); sc[t] = e; sum += e; }
-    sum = pf_block_sum(sum, red);
-    const float inv = 1.0f / sum;
-    __shared__ float part[256];
-    const uint32_t d = tid % headDim, ph = tid / headDim, nph = 256 / headDim;
-    float acc = 0.0f;
-    if (ph < nph)
-        for (uint32_t t = ph; t < nTok; t += nph) acc += sc[t] * vCache[((size_t)t * numHeads + head) * headDim + d];
-    part[tid] = acc;
-    __syncthreads();
-    if (tid < headDim) {
-        float s2 = 0.0f;
-        for (uint32_t p = 0; p < nph; p++) s2 += part[p * headDim + tid];
-        out[head * headDim + tid] = s2 * inv;
-    }
-}
-
-hipError_t launch_fetch_rows(const uint16_t* emb, const uint32_t* ids, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
-    hipLaunchKernelGGL(fetch_rows_kernel, dim3((n + 255) / 256, rows), dim3(256), 0, st, emb, ids, out, n);
-    return hipGetLastError();
-}
-hipError_t launch_add_rmsnorm_mul_rows(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, uint32_t rows, hipStream_t st) {
-    hipLaunchKernelGGL(add_rmsnorm_mul_rows_kernel, dim3(rows), dim3(1024), 0, st, h, delta, w, out, n);
-    return hipGetLastError();
-}
-hipError_t launch_rope_kv_rows(const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache, uint32_t pos0,
-                               uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, hipStream_t st) {
-    hipLaunchKernelGGL(rope_kv_rows_kernel, dim3(numHeads, rows), dim3(headDim), 0, st, xq, xk, xv, qOut, kCache, vCache, pos0, numHeads,
-                       numHeads / numHeadsKV, logf(ropeBase));
-    return hipGetLastError();
-}
-hipError_t launch_attention_rows(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
-                                 uint32_t numHeads, uint32_t headDim, hipStream_t st) {
-    hipLaunchKernelGGL(attention_rows_kernel, dim3(numHeads, rows), dim3(256), (pos0 + rows) * sizeof(float), st, q, kCache, vCache, pos0, out,
-                       numHeads, headDim);
     return hipGetLastError();
 }
 

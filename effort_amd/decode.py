@@ -15,7 +15,7 @@ spends ~15 ms/token in such gaps, runNetwork.swift:91-103).  torch is used for b
 reference compares against (``effort`` 100 % vs dense, KL divergence of the logits).
 
 ``Decoder.prefill`` / ``run(..., prefill=True)`` ingest a prompt in blocks of up to 64 tokens that share one pass over every
-matrix (the MFMA block multiply and the block forms of the glue, effort_amd/csrc/prefill.hip), eagerly, beside the token step:
+matrix (the MFMA block multiply, effort_amd/csrc/prefill.hip; the block forms of the glue, effort_amd/csrc/decode.hip), eagerly, beside the token step:
 the step, its graphs and the cache layout are the same with or without it.
 """
 from __future__ import annotations

@@ -1,4 +1,4 @@
-"""Prompt prefill on the GPU (effort_amd/csrc/prefill.hip, Decoder.prefill).
+"""Prompt prefill on the GPU (effort_amd/csrc/prefill.hip, the block glue in effort_amd/csrc/decode.hip, Decoder.prefill).
 
   1. effort_dense_gemm_rows against the float64 reference of basicMul (tests/glue_reference.py: dense), row by row, at the bar the
      in-tree GEMV meets with the same exact f16 products and f32 sums: ``dense_close`` with DENSE_BAND = 1e-5.  An MFMA step sums 32
@@ -162,6 +162,7 @@ def test_rows_do_not_depend_on_the_block(gpu):
 # ---------------------------------------------------------------- 3. the block glue equals the single-token entry points
 HEADS, HEADS_KV, MAX_TOKENS = 8, 2, 32
 GLUE = [(hd, pos0, rows) for hd in (64, 128) for pos0 in (0, 5) for rows in (1, 3, 17)]
+GLUE.append((256, 5, 3))                                             # headDim 256: the one head size at which attention has a single value phase
 
 
 def rnd(seed, *shape):

@@ -60,6 +60,12 @@ struct effort_ctx {
     size_t xhRowsElems = 0;
     float* d_gemmPart = nullptr;      // effort_dense_gemm_rows: the k splits' partial sums
     size_t gemmPartFloats = 0;
+    uint16_t* d_xhRouted = nullptr;   // effort_dense_gemm_rows_routed: its OWN three (a captured effort_dense_gemm_rows keeps the block multiply's addresses)
+    size_t xhRoutedElems = 0;
+    float* d_routedPart = nullptr;
+    size_t routedPartFloats = 0;
+    uint32_t* d_routedGroups = nullptr;   // per-expert counts and assignment lists (a fixed size)
+    size_t routedGroupWords = 0;
     float* d_cos = nullptr;
     uint16_t* d_convVals = nullptr;   // converter scratch (transposed matrix)
     size_t convElems = 0;
@@ -383,7 +389,7 @@ extern "C" void effort_destroy(effort_ctx* c) {
     if (c->ev) { for (int i = 0; i < effort_ctx::kMaxSamples * 4; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]); delete[] c->ev; }
     for (int i = 0; i < effort_ctx::kMaxLanes; i++) lane_free(c->device, c->lane[i]);
     pool_put(c->device, c->forkEv);
-    hipFree(c->d_blockScratch); hipFree(c->d_vhalf); hipFree(c->d_xhRows); hipFree(c->d_gemmPart); hipFree(c->d_cos); hipFree(c->d_convVals); hipFree(c->d_status); hipFree(c->d_tstamp);
+    hipFree(c->d_blockScratch); hipFree(c->d_vhalf); hipFree(c->d_xhRows); hipFree(c->d_gemmPart); hipFree(c->d_xhRouted); hipFree(c->d_routedPart); hipFree(c->d_routedGroups); hipFree(c->d_cos); hipFree(c->d_convVals); hipFree(c->d_status); hipFree(c->d_tstamp);
     delete c;
 }
 
@@ -1090,6 +1096,45 @@ extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float*
     if (grc != EFFORT_OK) return grc;
     HIP_TRY(c, launch_dense_gemm_rows(static_cast<const uint16_t*>(W), x, c->d_xhRows, c->d_gemmPart, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows,
                                       c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_dense_gemm_rows_routed(effort_ctx* c, const void* W, int numExperts, const uint32_t* idx2, const float* x, int xPerSlot, float* out,
+                                             int inDim, int outDim, int rows) {
+    if (inDim <= 0 || outDim <= 0 || numExperts <= 0 || !prefill_rows_ok(rows) || (xPerSlot != 0 && xPerSlot != 1))
+        return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows_routed: inDim, outDim, numExperts >= 1, 1 <= rows <= 64, xPerSlot 0 / 1");
+    if (!dense_gemm_rows_supported((uint32_t)inDim, (uint32_t)outDim) || numExperts > 64)
+        return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows_routed: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, one expert below 4 GiB, numExperts <= 64");
+    if (!c || !W || !idx2 || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows_routed: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    // (grown to a full block's worth whatever xPerSlot and rows are: the w1, w3 and w2 calls of a layer allocate once)
+    const size_t xRows = (size_t)(xPerSlot ? 2 : 1) * rows;
+    int grc = grow_scratch(c, c->d_xhRouted, c->xhRoutedElems, xRows * inDim, (size_t)2 * EFFORT_PREFILL_MAX_ROWS * inDim);
+    if (grc == EFFORT_OK)
+        grc = grow_scratch(c, c->d_routedPart, c->routedPartFloats, dense_gemm_rows_routed_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows),
+                           dense_gemm_rows_routed_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS));
+    if (grc == EFFORT_OK)
+        grc = grow_scratch(c, c->d_routedGroups, c->routedGroupWords, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words());
+    if (grc != EFFORT_OK) return grc;
+    HIP_TRY(c, launch_dense_gemm_rows_routed(static_cast<const uint16_t*>(W), (uint32_t)numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted, c->d_routedPart,
+                                             c->d_routedGroups, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_moe_route_rows(effort_ctx* c, const float* h, const void* normW, const void* gateW, int n, int numExperts, float* gateOut,
+                                     uint32_t* idx2, float* val2, int rows) {
+    if (n <= 0 || numExperts <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "moe_route_rows: n, numExperts >= 1, 1 <= rows <= 64");
+    if (!moe_route_supported((uint32_t)n, (uint32_t)numExperts))
+        return fail(c, EFFORT_ERR_SHAPE, "moe_route_rows: n % 16 == 0, 16 <= n <= 16384, 1 <= numExperts <= 64");
+    if (!c || !h || !normW || !gateW || !idx2 || !val2) return fail(c, EFFORT_ERR_ARG, "moe_route_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_moe_route_rows(h, static_cast<const uint16_t*>(normW), static_cast<const uint16_t*>(gateW), (uint32_t)n, (uint32_t)numExperts, gateOut,
+                                     idx2, val2, (uint32_t)rows, c->stream));
+    return EFFORT_OK;
+}
+extern "C" int effort_mix2_add_rows(effort_ctx* c, float* h, const float* f, const float* val2, int n, int rows) {
+    if (n <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "mix2_add_rows: n >= 1, 1 <= rows <= 64");
+    if (!c || !h || !f || !val2) return fail(c, EFFORT_ERR_ARG, "mix2_add_rows: null argument");
+    { const int jrc = join_lanes(c); if (jrc != EFFORT_OK) return jrc; }
+    HIP_TRY(c, launch_mix2_add_rows(h, f, val2, (uint32_t)n, (uint32_t)rows, c->stream));
     return EFFORT_OK;
 }
 extern "C" int effort_fetch_rows(effort_ctx* c, const void* emb, const uint32_t* ids, float* out, int n, int rows) {

@@ -12,7 +12,7 @@
 //                    bit for bit what add_rmsnorm_mul -> dense_gemv_kernel<1, 0> -> top2_softmax write in a row
 //   mix2_add         h += f0 * val[0] + f1 * val[1]: mix2 and the residual add the next norm would have done (runNetwork.swift:190-199)
 //   argmax           greedy pick of the next token (the reference takes mpsTopK[0], helpers/mps.swift:52-84), pos += 1
-// add_rmsnorm_mul, rope_kv, attention and fetch_row each have a block form (*_rows) over `rows` tokens for prompt prefill: one workgroup
+// add_rmsnorm_mul, rope_kv, attention, fetch_row, moe_route and mix2_add each have a block form (*_rows) over `rows` tokens for prompt prefill: one workgroup
 // (fetch: one grid row) per token, running the SAME body as the token form -- per token it writes the token form's bits.
 #include "effort_internal.h"
 
@@ -398,10 +398,19 @@ __global__ void mix2_kernel(const float* __restrict__ f0, const float* __restric
 }
 
 // h += f0 * val[0] + f1 * val[1]: mix2_kernel's expression, then the one f32 add the next add_rmsnorm_mul would have performed
-__global__ void mix2_add_kernel(float* __restrict__ h, const float* __restrict__ f0, const float* __restrict__ f1,
-                                const float* __restrict__ val, uint32_t n) {
+__device__ __forceinline__ void mix2_add_row(float* __restrict__ h, const float* __restrict__ f0, const float* __restrict__ f1,
+                                             const float* __restrict__ val, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) h[i] = h[i] + (f0[i] * val[0] + f1[i] * val[1]);
+}
+__global__ void mix2_add_kernel(float* __restrict__ h, const float* __restrict__ f0, const float* __restrict__ f1,
+                                const float* __restrict__ val, uint32_t n) {
+    mix2_add_row(h, f0, f1, val, n);
+}
+// grid = (ceil(n / 256), rows): row blockIdx.y of h [rows][n], f [rows][2][n] (f0 = f[r][0], f1 = f[r][1]) and val [rows][2]
+__global__ void mix2_add_rows_kernel(float* __restrict__ h, const float* __restrict__ f, const float* __restrict__ val, uint32_t n) {
+    const size_t r = blockIdx.y;
+    mix2_add_row(h + r * n, f + 2u * r * n, f + (2u * r + 1u) * n, val + 2u * r, n);
 }
 
 // Mixtral routing in ONE launch of one workgroup (16 waves): x = rmsNorm(h) * w -> gate[e] = gateW[e] . f16(x) -> top-2 + softmax.
@@ -416,12 +425,11 @@ __global__ void mix2_add_kernel(float* __restrict__ h, const float* __restrict__
 // LDS hand-over of f16(x) and the dot products.  n % 16 == 0, 16 <= n <= kRouteMaxN, 1 <= numExperts <= kRouteMaxExperts (the launcher's caller checks).
 constexpr uint32_t kRouteMaxN = 16384, kRouteMaxExperts = 64;
 typedef _Float16 route_half2 __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(1024) void moe_route_kernel(const float* __restrict__ h, const uint16_t* __restrict__ w,
-                                                         const uint16_t* __restrict__ gateW, uint32_t n, uint32_t numExperts,
-                                                         float* __restrict__ gateOut, uint32_t* __restrict__ idx, float* __restrict__ val) {
-    __shared__ __attribute__((aligned(16))) uint16_t xh[kRouteMaxN];          // f16(x), padded with zeros to a multiple of 512
-    __shared__ float red[17];
-    __shared__ float logit[kRouteMaxExperts];
+// One token, block = 1024.  xh [kRouteMaxN] (16-byte aligned): f16(x), padded with zeros to a multiple of 512; red [17]; logit [kRouteMaxExperts].
+__device__ __forceinline__ void moe_route_row(const float* __restrict__ h, const uint16_t* __restrict__ w,
+                                              const uint16_t* __restrict__ gateW, uint32_t n, uint32_t numExperts,
+                                              float* __restrict__ gateOut, uint32_t* __restrict__ idx, float* __restrict__ val,
+                                              uint16_t* xh, float* red, float* logit) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t padded = (n + 511u) / 512u * 512u;
     constexpr int K = 4, U = 8;
@@ -500,6 +508,24 @@ __global__ __launch_bounds__(1024) void moe_route_kernel(const float* __restrict
     __syncthreads();
     if (tid == 0) top2_softmax_scan(logit, numExperts, idx, val);
 }
+__global__ __launch_bounds__(1024) void moe_route_kernel(const float* __restrict__ h, const uint16_t* __restrict__ w,
+                                                         const uint16_t* __restrict__ gateW, uint32_t n, uint32_t numExperts,
+                                                         float* __restrict__ gateOut, uint32_t* __restrict__ idx, float* __restrict__ val) {
+    __shared__ __attribute__((aligned(16))) uint16_t xh[kRouteMaxN];
+    __shared__ float red[17];
+    __shared__ float logit[kRouteMaxExperts];
+    moe_route_row(h, w, gateW, n, numExperts, gateOut, idx, val, xh, red, logit);
+}
+// grid = rows, block = 1024: row blockIdx.x of h [rows][n], gateOut [rows][numExperts] (may be null), idx and val [rows][2]
+__global__ __launch_bounds__(1024) void moe_route_rows_kernel(const float* __restrict__ h, const uint16_t* __restrict__ w,
+                                                              const uint16_t* __restrict__ gateW, uint32_t n, uint32_t numExperts,
+                                                              float* __restrict__ gateOut, uint32_t* __restrict__ idx, float* __restrict__ val) {
+    __shared__ __attribute__((aligned(16))) uint16_t xh[kRouteMaxN];
+    __shared__ float red[17];
+    __shared__ float logit[kRouteMaxExperts];
+    const size_t r = blockIdx.x;
+    moe_route_row(h + r * n, w, gateW, n, numExperts, gateOut ? gateOut + r * numExperts : nullptr, idx + 2u * r, val + 2u * r, xh, red, logit);
+}
 
 hipError_t launch_top2_softmax(const float* gate, uint32_t n, uint32_t* idx, float* val, hipStream_t st) {
     hipLaunchKernelGGL(top2_softmax_kernel, dim3(1), dim3(64), 0, st, gate, n, idx, val);
@@ -519,6 +545,15 @@ bool moe_route_supported(uint32_t n, uint32_t numExperts) {
 hipError_t launch_moe_route(const float* h, const uint16_t* w, const uint16_t* gateW, uint32_t n, uint32_t numExperts, float* gateOut,
                             uint32_t* idx, float* val, hipStream_t st) {
     hipLaunchKernelGGL(moe_route_kernel, dim3(1), dim3(1024), 0, st, h, w, gateW, n, numExperts, gateOut, idx, val);
+    return hipGetLastError();
+}
+hipError_t launch_moe_route_rows(const float* h, const uint16_t* w, const uint16_t* gateW, uint32_t n, uint32_t numExperts, float* gateOut,
+                                 uint32_t* idx, float* val, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(moe_route_rows_kernel, dim3(rows), dim3(1024), 0, st, h, w, gateW, n, numExperts, gateOut, idx, val);
+    return hipGetLastError();
+}
+hipError_t launch_mix2_add_rows(float* h, const float* f, const float* val, uint32_t n, uint32_t rows, hipStream_t st) {
+    hipLaunchKernelGGL(mix2_add_rows_kernel, dim3((n + 255) / 256, rows), dim3(256), 0, st, h, f, val, n);
     return hipGetLastError();
 }
 hipError_t launch_add_rmsnorm_mul(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, hipStream_t st) {

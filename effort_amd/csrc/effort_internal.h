@@ -258,19 +258,28 @@ hipError_t launch_moe_route(const float* h, const uint16_t* w, const uint16_t* g
                             uint32_t* idx, float* val, hipStream_t st);
 hipError_t launch_argmax(const float* logits, uint32_t n, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
                          int* status, hipStream_t st);
-// ... the block forms of four of them, one workgroup (fetch: one grid row) per token of a prefill block
+// ... the block forms of six of them, one workgroup (fetch, mix2_add: one grid row) per token of a prefill block
 hipError_t launch_fetch_rows(const uint16_t* emb, const uint32_t* ids, float* out, uint32_t n, uint32_t rows, hipStream_t st);
 hipError_t launch_add_rmsnorm_mul_rows(float* h, const float* delta, const uint16_t* w, float* out, uint32_t n, uint32_t rows, hipStream_t st);
 hipError_t launch_rope_kv_rows(const float* xq, const float* xk, const float* xv, float* qOut, float* kCache, float* vCache, uint32_t pos0,
                                uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, hipStream_t st);
 hipError_t launch_attention_rows(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
                                  uint32_t numHeads, uint32_t headDim, hipStream_t st);
+hipError_t launch_moe_route_rows(const float* h, const uint16_t* w, const uint16_t* gateW, uint32_t n, uint32_t numExperts, float* gateOut,
+                                 uint32_t* idx, float* val, uint32_t rows, hipStream_t st);
+hipError_t launch_mix2_add_rows(float* h, const float* f, const float* val, uint32_t n, uint32_t rows, hipStream_t st);
 
 // prompt prefill (prefill.hip): the block multiply
 bool dense_gemm_rows_supported(uint32_t inDim, uint32_t outDim);
 size_t dense_gemm_rows_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows);      // scratch for the k splits' partial sums (0: none)
 hipError_t launch_dense_gemm_rows(const uint16_t* W_f16, const float* x, uint16_t* xhScratch /* rows * inDim halves */, float* partScratch, float* out,
                                   uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
+// ... and its routed form: assignment 2 r + s multiplies expert idx2[2 r + s] of a stack (numExperts <= 64)
+size_t dense_gemm_rows_routed_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows);
+size_t dense_gemm_rows_routed_group_words();                                              // scratch for the per-expert counts and assignment lists
+hipError_t launch_dense_gemm_rows_routed(const uint16_t* W_f16, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot,
+                                         uint16_t* xhScratch /* (xPerSlot ? 2 : 1) * rows * inDim halves */, float* partScratch, uint32_t* groupScratch,
+                                         float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
 // prefill attention with the block's queries sharing each K / V tile (attention_block.hip): flash-style, f32 MFMA, headDim 64 / 128 / 256
 hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
                                   uint32_t numHeads, uint32_t headDim, hipStream_t st);

@@ -475,6 +475,14 @@ class Decoder:
         self.pf_attnOutput, self.pf_attnFfnOut, self.pf_ffnOut = f(q), f(cfg.stateDim), f(cfg.stateDim)
         self.pf_x1, self.pf_x3, self.pf_x2 = f(cfg.hiddenDim), f(cfg.hiddenDim), f(cfg.hiddenDim)
         self.pf_ids = torch.zeros(chunk, dtype=torch.int32, device=dev)
+        if self.moe:
+            # ffn="routed": [chunk][2][.] per assignment (token, slot of its top-2); the routing of the LAST block is kept per layer --
+            # rows [n][r] of pf_gateIdxs (the expert pair) and pf_gateOut (the gate logits) -- for whoever wants to look at it
+            f2 = lambda n: torch.zeros((chunk, 2, n), dtype=torch.float32, device=dev)  # noqa: E731
+            self.pf_x1r, self.pf_x3r, self.pf_x2r, self.pf_ffnOutR = f2(cfg.hiddenDim), f2(cfg.hiddenDim), f2(cfg.hiddenDim), f2(cfg.stateDim)
+            self.pf_gateVals = torch.zeros((chunk, 2), dtype=torch.float32, device=dev)
+            self.pf_gateIdxs = torch.zeros((cfg.numLayers, chunk, 2), dtype=torch.int32, device=dev)
+            self.pf_gateOut = torch.zeros((cfg.numLayers, chunk, cfg.numExperts), dtype=torch.float32, device=dev)
         self._pf = chunk
 
     def _gemm_rows(self, x, core, out, rows: int):
@@ -488,7 +496,21 @@ class Decoder:
             return
         g.check(rc, "dense_gemm_rows")
 
-    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows"):
+    def _gemm_rows_routed(self, x, cores, idx2, out, rows: int, per_slot: bool):
+        """out[r][s] = cores[idx2[r][s]] * f16(x[r]) -- ``per_slot``: * f16(x[r][s]) -- for the first ``rows`` tokens: every picked expert's
+        matrix is read ONCE for all the tokens that picked it (effort_dense_gemm_rows_routed).  A stack the kernel refuses
+        (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMulExpert`` per assignment, as ``_gemm_rows`` falls back."""
+        g = self.g
+        E, o, i = (int(d) for d in cores.shape)
+        rc = _lib.lib().effort_dense_gemm_rows_routed(g.ctx, _p(cores), E, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), i, o, rows)
+        if rc == -2:
+            for r in range(rows):
+                for sl in range(2):
+                    basicMulExpert(x[r][sl] if per_slot else x[r], cores, idx2[r][sl:sl + 1], out[r][sl])
+            return
+        g.check(rc, "dense_gemm_rows_routed")
+
+    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense"):
         """Ingest prompt tokens in bulk: fill ``kCache`` / ``vCache`` rows ``pos0 .. pos0 + T - 1`` of every layer, in blocks of at most
         ``chunk`` (<= 64) tokens that share ONE pass over each matrix, then set ``pos`` to ``pos0 + T``.  No logits, no pick: the next
         ``token_step`` (or graph replay) continues from the caches.  Eager, never captured: ``pos0`` and the block sizes are host values.
@@ -505,18 +527,34 @@ class Decoder:
         MFMA with an online softmax, within the f32 bar of the same float64 value but not the same bits.  On either path the caches
         do not depend on ``chunk``.
 
+        ``ffn``: ``"dense"``, the default, is the walk above and serves dense-FFN models only.  ``"routed"`` serves a Mixtral model (FP16,
+        an ffnGate in every layer, numExperts >= 2, the expert stacks' cores [E, out, in] kept): the second half of a layer becomes
+        norm -> effort_moe_route_rows (every token's top-2 and their weights, on the device) -> w1 and w3 as routed block multiplies
+        (effort_dense_gemm_rows_routed: the block's tokens grouped by the expert they picked, each picked expert's matrix read once per
+        block, out [rows][2][hiddenDim]) -> silu over both slots -> routed w2 -> effort_mix2_add_rows on the block's h; nothing is
+        pending afterwards.  Still the dense arithmetic, still chunk-independent bits (a routed product is the block multiply's for
+        that token alone).  The last block's routing stays in ``pf_gateIdxs[layer][row]`` / ``pf_gateOut[layer][row]``.
+
         Raises ValueError, before anything is enqueued: a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
-        them), a Mixtral model, a column-sharded decoder, ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other
-        than ``"rows"`` / ``"block"``."""
+        them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
+        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"``, an ``ffn`` other
+        than ``"dense"`` / ``"routed"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
         T = len(ids)
-        if self.moe or cfg.numExperts > 1:
+        if ffn not in ("dense", "routed"):
+            raise ValueError(f"Decoder.prefill: ffn must be 'dense' or 'routed', not {ffn!r}")
+        routed = ffn == "routed"
+        if routed and not (cfg.numExperts >= 2 and all(L.ffnGate is not None and L.ffnGate.dtype == torch.float16 for L in m.layers)):
+            raise ValueError("Decoder.prefill: ffn='routed' is for Mixtral models (an f16 ffnGate in every layer, numExperts >= 2)")
+        if not routed and (self.moe or cfg.numExperts > 1):
             raise ValueError("Decoder.prefill: dense-FFN models only (a Mixtral layer routes per token)")
         if self.sharded:
             raise ValueError("Decoder.prefill: not implemented for the column-sharded decode loop")
         if any(getattr(L, w).core is None for L in m.layers for w in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")):
             raise ValueError("Decoder.prefill: every bundle needs its f16 core (Model.random(keep_cores=True), or a Q4 model)")
+        if routed and any(getattr(L, w).core.dim() != 3 or int(getattr(L, w).core.shape[0]) != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
+            raise ValueError("Decoder.prefill: ffn='routed' needs the expert stacks' cores [numExperts, out, in] (Model.random(keep_cores=True))")
         if not 1 <= chunk <= self.PREFILL_MAX_ROWS:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
@@ -546,6 +584,17 @@ class Decoder:
                 ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim, self.maxTokens), attendName)
                 self._gemm_rows(self.pf_attnOutput, L.wo.core, self.pf_attnFfnOut, rows)
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
+                if routed:
+                    idx2 = self.pf_gateIdxs[n]
+                    ck(lib.effort_moe_route_rows(g.ctx, _p(self.pf_h), _p(L.ffnNorm), _p(L.ffnGate), cfg.stateDim, cfg.numExperts, _p(self.pf_gateOut[n]),
+                                                 _p(idx2), _p(self.pf_gateVals), rows), "moe_route_rows")
+                    self._gemm_rows_routed(self.pf_norm, L.w1.core, idx2, self.pf_x1r, rows, False)
+                    self._gemm_rows_routed(self.pf_norm, L.w3.core, idx2, self.pf_x3r, rows, False)
+                    ck(lib.effort_silu_mul(g.ctx, _p(self.pf_x1r), _p(self.pf_x3r), _p(self.pf_x2r), rows * 2 * cfg.hiddenDim), "silu")
+                    self._gemm_rows_routed(self.pf_x2r, L.w2.core, idx2, self.pf_ffnOutR, rows, True)
+                    ck(lib.effort_mix2_add_rows(g.ctx, _p(self.pf_h), _p(self.pf_ffnOutR), _p(self.pf_gateVals), cfg.stateDim, rows), "mix2_add_rows")
+                    delta = None                           # the mix landed on h
+                    continue
                 self._gemm_rows(self.pf_norm, L.w1.core, self.pf_x1, rows)
                 self._gemm_rows(self.pf_norm, L.w3.core, self.pf_x3, rows)
                 ck(lib.effort_silu_mul(g.ctx, _p(self.pf_x1), _p(self.pf_x3), _p(self.pf_x2), rows * cfg.hiddenDim), "silu")
@@ -584,7 +633,7 @@ class Decoder:
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
             collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64,
-            prefill_attention: str = "rows"):
+            prefill_attention: str = "rows", prefill_ffn: str = "dense"):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
@@ -594,7 +643,8 @@ class Decoder:
         and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
-        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``).
+        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
+        ``"routed"``: a Mixtral prompt prefills only with ``"routed"``).
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
@@ -610,7 +660,7 @@ class Decoder:
         if skip:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention)
+            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn)
             torch.cuda.synchronize()
             self.last_prefill_s = time.perf_counter() - tp
         for step in range(skip, numTokens):

@@ -366,6 +366,33 @@ EFFORT_API int effort_decode_status(effort_ctx* ctx, int* host_out);
  * either buffer: before capturing, call it eagerly with 64 rows once for EVERY (inDim, outDim) pair the context will ever see.
  * Up to three launches: convert, multiply, and the reduce when the shape has more than one split. */
 EFFORT_API int effort_dense_gemm_rows(effort_ctx* ctx, const void* W_f16_dev, const float* x_dev, float* out_dev, int inDim, int outDim, int rows);
+/* The ROUTED block multiply (a Mixtral block): W f16 [numExperts][outDim][inDim], one expert's matrix as effort_dense_gemm_rows takes it.
+ * Assignment a = 2 r + s (token r < rows, slot s of its top-2) multiplies expert e = min(idx2_dev[a], numExperts - 1) -- the clamp of
+ * effort_dense_gemv_expert: a device value cannot be refused by a return code.  Its input row is x[r] when xPerSlot == 0 (w1 / w3: both
+ * slots read the token's normed state; x f32 [rows][inDim]) and x[a] when xPerSlot == 1 (w2: a gated vector per slot; x f32
+ * [2 * rows][inDim]); out[a] = W[e] * f16(input), out f32 [rows][2][outDim].
+ * The assignments are grouped by expert on the device, in assignment order (the expert numbers never reach the host); an expert's
+ * workgroups stream its matrix ONCE for all its token columns (64 columns a walk: 65 .. 128 assignments on one expert, which only
+ * duplicates or clamping produce, walk it again), and an expert nobody picked is not read.
+ * CONTRACT: out[a] is BIT FOR BIT what effort_dense_gemm_rows(ctx, W + e * outDim * inDim, input, ., inDim, outDim, 1) writes: the
+ * same k split, the same order of the sums, zero operands for dead columns.  So it depends on the input row and W[e] alone -- not on
+ * rows, not on a, not on who else picked e.  No x row and no idx2 entry at or past rows (xPerSlot == 1: x rows past 2 * rows) is read;
+ * nothing outside out[0 .. 2 * rows * outDim) is written.
+ * Shapes: one expert's (inDim, outDim) as effort_dense_gemm_rows serves them (ONE expert below 4 GiB: the stack may be larger),
+ * numExperts <= 64; anything else returns EFFORT_ERR_SHAPE (the caller falls back to effort_dense_gemv_expert per assignment).
+ * xPerSlot other than 0 / 1, numExperts < 1: EFFORT_ERR_ARG.  The weight stream is nt when ONE expert's matrix is above 64 MiB.
+ * Uses context scratch of its own, shared with no other entry point: 128 * inDim halves for f16(x), splits * 128 * outDim floats for
+ * the partial sums of the k split, and 64 * 129 words for the groups.  The first two only grow, by effort_dense_gemm_rows's rule, and the
+ * same advice holds before capturing.  Up to three launches: convert + group, multiply, and the reduce when the shape has more than
+ * one split. */
+EFFORT_API int effort_dense_gemm_rows_routed(effort_ctx* ctx, const void* W_f16_dev, int numExperts, const uint32_t* idx2_dev, const float* x_dev,
+                                  int xPerSlot, float* out_dev, int inDim, int outDim, int rows);
+/* Block forms of the Mixtral glue, per row BIT FOR BIT the token forms (the same body):
+ * effort_moe_route_rows: effort_moe_route on row r of h [rows][n]; idx2 / val2 [rows][2], gate_out (may be NULL) [rows][numExperts].
+ * effort_mix2_add_rows: effort_mix2_add on row r of h [rows][n] with f0 = f[r][0], f1 = f[r][1] (f f32 [rows][2][n]) and val2[r]. */
+EFFORT_API int effort_moe_route_rows(effort_ctx* ctx, const float* h_dev, const void* norm_w_f16_dev, const void* gate_f16_dev, int n, int numExperts,
+                          float* gate_out_dev, uint32_t* idx2_dev, float* val2_dev, int rows);
+EFFORT_API int effort_mix2_add_rows(effort_ctx* ctx, float* h_dev, const float* f_dev, const float* val2_dev, int n, int rows);
 /* Block forms of the glue: per row, BIT FOR BIT what the single-token entry point writes (the same sums in the same order).
  * effort_fetch_rows: out[r] = row ids_dev[r] of the table (effort_fetch_row).
  * effort_add_rmsnorm_mul_rows: effort_add_rmsnorm_mul on row r of h, delta (may be NULL) and out; one norm weight vector.

@@ -10,7 +10,9 @@ record also goes to profiles/r08_decode_sampled.json) and `decode_prefill` (prom
 beside the dense GEMV on rotating matrices, and a 256-token prompt through `Decoder.prefill` beside the token-by-token loop; its
 record also goes to profiles/r09_prefill.json; asked for alone, it skips the headline job and its matrix sets) and `prefill_attention`
 (effort_attention_rows beside effort_attention_block on rotating caches, and 256- and 2048-token prompts through `Decoder.prefill` on
-both attention paths; its record also goes to profiles/r10_prefill_attention.json; standalone like `decode_prefill`).
+both attention paths; its record also goes to profiles/r10_prefill_attention.json; standalone like `decode_prefill`) and
+`prefill_mixtral` (a Mixtral prompt: the routed block multiply beside 8 dense block calls, and Decoder.prefill(ffn="routed") beside the
+token loop; its record also goes to profiles/r11_prefill_mixtral.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -27,8 +29,9 @@ sys.path.insert(0, ROOT)
 import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
-            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention")
-STANDALONE = ("decode_prefill", "prefill_attention")             # sections that read neither the headline nor the matrix sets of bench.Bench
+            "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
+            "prefill_mixtral")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral")             # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -526,6 +529,127 @@ def decode_prefill(b, res):
     del dec, model
 
 
+def prefill_mixtral(b, res):
+    """Mixtral prompt ingest.  Kernel legs, decode_prefill's protocol: effort_dense_gemm_rows_routed on 4096 -> 14336 x 8 experts and
+    14336 -> 4096 x 8 at 16 and 64 rows under a uniform random routing (two different experts per token), beside effort_dense_gemm_rows
+    on every expert's matrix of the same stacks at the same rows -- 8 of those calls stream the bytes one routed call streams when
+    every expert is picked.  Two stacks in rotation (1.9 GB).  Model legs, Mixtral-8x7B shapes with decode_mixtral's 8 layers, a
+    256-token prompt, one process, in this order: token by token dense, token by token at 25 % effort, prefill(ffn="routed") at chunk
+    16 and 64, the first leg again; ms per prompt token each, and the spread of the two dense token-loop legs."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(78)
+    E = 8
+
+    def us_per_call(fn, calls):
+        g._bind_stream()
+        fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            fn()
+        g._bind_stream()
+        for _ in range(3):
+            gr.replay()
+        torch.cuda.synchronize()
+        best = float("inf")
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
+        return best
+
+    kern = {"protocol": "one pass over two rotating stacks per graph, 4 replays per window, best of 3 windows, device events; routing: two "
+                        "different experts per token, uniform; dense_x8 = 8 x the time of one effort_dense_gemm_rows call on an expert's matrix"}
+    for outD, inD in ((14336, 4096), (4096, 14336)):
+        stacks = [torch.stack([(torch.randn((outD, inD), generator=gen, device=b.dev, dtype=torch.float32) * 0.02).to(torch.float16) for _ in range(E)])
+                  for _ in range(2)]
+        x = torch.randn((128, inD), generator=gen, device=b.dev, dtype=torch.float32)
+        out = torch.zeros((128, outD), device=b.dev)
+        idx2 = torch.stack([torch.randperm(E, generator=gen, device=b.dev)[:2] for _ in range(64)]).to(torch.int32).contiguous()
+        row = {"stacks": 2, "stack_bytes": E * outD * inD * 2}
+        for rows in (16, 64):
+            def routed(rows=rows):
+                g._bind_stream()
+                for W in stacks:
+                    g.check(lib.effort_dense_gemm_rows_routed(g.ctx, p(W), E, p(idx2), p(x), 0, p(out), inD, outD, rows), "dense_gemm_rows_routed")
+
+            def dense(rows=rows):
+                g._bind_stream()
+                for W in stacks:
+                    for e in range(E):
+                        g.check(lib.effort_dense_gemm_rows(g.ctx, p(W[e]), p(x), p(out), inD, outD, rows), "dense_gemm_rows")
+            picked = len(set(idx2[:rows].reshape(-1).tolist()))
+            r_us, d_us = us_per_call(routed, 2), 8 * us_per_call(dense, 2 * E)
+            row[f"rows_{rows}"] = {"experts_picked": picked, "routed_us_per_call": round(r_us, 2), "dense_x8_us": round(d_us, 2),
+                                   "routed_over_dense_x8": round(r_us / d_us, 3),
+                                   "routed_TBps_of_picked_bytes": round(picked * outD * inD * 2 / r_us / 1e6, 3)}
+        kern[f"{inD}->{outD}x{E}"] = row
+        del stacks, x, out
+        torch.cuda.empty_cache()
+    out = {"kernel": kern}
+
+    nprompt, layers = 256, 8
+    model = Model.random(MistralConfig(numLayers=layers, numExperts=E), seed=1, structured=True)
+    dec = Decoder(model, maxTokens=nprompt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+
+    def token_loop(**kw):
+        best = float("inf")
+        for _ in range(2):
+            _, dt, _ = dec.run(prompt, nprompt, **kw)
+            best = min(best, dt)
+        return round(best * 1e3, 4)
+
+    def prefill(chunk):
+        dec.prefill(prompt, chunk=chunk, ffn="routed")            # the warm call: it makes the buffers and warms the kernels; not timed
+        best = float("inf")
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dec.prefill(prompt, chunk=chunk, ffn="routed")
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t0)
+        return round(best * 1e3 / nprompt, 4)
+    m = {"model": "Mixtral-8x7B shapes (4096 / 14336, 8 experts, top-2, 32 / 8 heads), 8 layers, STRUCTURED random weights, seed 1",
+         "prompt_tokens": nprompt,
+         "protocol": "token loop: hipGraph replay of the step, timed from the 3rd step, best of 2 runs (LM head and pick in it); prefill: eager, "
+                     "synchronised wall time of Decoder.prefill(ffn='routed') over the whole prompt, best of 3 after a warm call (no LM head, the "
+                     "last layer stops after its cache write)"}
+    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dense=True)
+    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(effort=0.25)
+    m["prefill_routed_chunk_16_ms_per_prompt_token"] = prefill(16)
+    m["prefill_routed_chunk_64_ms_per_prompt_token"] = prefill(64)
+    m["token_by_token_dense_again_ms_per_prompt_token"] = token_loop(dense=True)
+    base, again = m["token_by_token_dense_ms_per_prompt_token"], m["token_by_token_dense_again_ms_per_prompt_token"]
+    m["token_loop_legs_spread"] = round(abs(base - again) / min(base, again), 4)
+    for k in ("token_by_token_effort_0.25", "prefill_routed_chunk_16", "prefill_routed_chunk_64"):
+        m[f"dense_token_loop_over_{k}"] = round(base / m[f"{k}_ms_per_prompt_token"], 2)
+    m["routed_chunk_64_faster_than_the_dense_token_loop"] = m["prefill_routed_chunk_64_ms_per_prompt_token"] < min(base, again)
+    out["model"] = m
+    res["prefill_mixtral"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r11_prefill_mixtral.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def prefill_attention(b, res):
     """Prefill attention: effort_attention_rows (every query of a block reads K / V again) beside effort_attention_block (the block's
     queries share each K / V tile), one process.  Kernel legs, decode_prefill's protocol: 32 heads, headDim 128, maxTokens 8192, a pass
@@ -645,7 +769,8 @@ def layer_latency(b, res):
 RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_contexts": four_contexts, "timeit_protocol": timeit_full,
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
-       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention}
+       "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
+       "prefill_mixtral": prefill_mixtral}
 
 
 class Light:

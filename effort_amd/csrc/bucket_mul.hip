@@ -295,7 +295,7 @@ __device__ __forceinline__ void stage_issue(const GroupKArgs& ga, const ItemRef&
     const uint32_t rowsPerIn = g.rowsPerIn, inDim = g.inDim, mask = (1u << lg) - 1u;
     const uint32_t nSlots = FMT == kFp16 ? (rowsPerIn << lg) : (nb << 3);
     constexpr bool compact = COMPACT && FMT == kFp16;              // a.stats = the row means alone, u16 per bucket row (persistent launches)
-    // (32-bit size and, below, 32-bit byte offsets: registration bounds the whole stack's stats, 8 bytes a bucket row, below 4 GiB -- api.hip, check_bundle)
+    // (32-bit size and, below, 32-bit byte offsets: registration bounds the whole stack's stats, 8 bytes a bucket row, below 4 GiB -- weights.hip, check_bundle)
     const u32x4 rs = make_rsrc(a.stats, (uint32_t)((size_t)g.numExperts * g.expertRows * (compact ? 2u : 8u)));
     const u32x4 rv = make_rsrc(a.v, inDim * 4u);
     const uint32_t ldsM = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lds_v*)(smem + lp.offM));
@@ -1340,7 +1340,7 @@ __global__ __launch_bounds__(64 * W, (FUSED && FMT != kFp16 && W == 2 ? 2 : W <=
     // traces profiles/r06_q4_timelines.txt) idles through every head and tail.  The workgroups placed second (block >= numCU: the dispatcher fills the
     // CUs round-robin -- speed only, never correctness) start `staggerSleeps` x ~0.9 us late and the pair runs out of step from then on.  Measured, Q4 alone on the
     // chip: 32 calls per launch 109.5 -> 99.8 us at 6-12 us, 16 calls as 768 items 85.4 -> 69.0; with four launches in flight it LOSES 2-5 % (the CU is
-    // busy anyway, the wait is just a wait), so the host asks for it only where launches do not overlap (api.hip: a context without lanes).
+    // busy anyway, the wait is just a wait), so the host asks for it only where launches do not overlap (mul.hip: a context without lanes).
     const uint32_t staggerSleeps = ga.staggerSleeps;
     if constexpr (PERSIST) {                    // (counted sleeps, not a clock: the shipped kernels read no clock at all)
         if (GA_PERSISTENT(ga) && staggerSleeps && blockIdx.x >= ga.numCU)
@@ -1481,12 +1481,12 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st, LaunchedV
     }
     bool fusedAny = false;
     for (uint32_t i = 0; i < ga.count; i++) fusedAny = fusedAny || ga.call[i].pre || ga.call[i].resid;
-    // (Q4: a prologue on a call whose outliers gather v from memory -- inDim > kOlLdsFloats -- would add the outliers of the RAW input: api.hip refuses it)
+    // (Q4: a prologue on a call whose outliers gather v from memory -- inDim > kOlLdsFloats -- would add the outliers of the RAW input: mul.hip refuses it)
     for (uint32_t i = 0; FMT != kFp16 && i < ga.count; i++)
         if (ga.call[i].pre && ga.call[i].ol.blockPtr && ga.geom[ga.call[i].geom].inDim > kOlLdsFloats) return hipErrorInvalidValue;
     // (every instantiation may use the whole LDS: bucket_mul_prepare_device, once per device at effort_create)
     if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
-    const bool compact = (ga.split & 4u) != 0u;                   // (api.hip: persistent FP16 launches of plain calls)
+    const bool compact = (ga.split & 4u) != 0u;                   // (plan.hip: persistent FP16 launches of plain calls)
     if (compact && (FMT != kFp16 || (fusedAny && !lean))) return hipErrorInvalidValue;
     const dim3 gd(grid), bd(64 * W);
     // the generic instantiation ignores the compact bit under a prologue / residual (refused above) and takes the plain means otherwise
@@ -1501,10 +1501,8 @@ static hipError_t launch_mul_t(const GroupKArgs& gaIn, hipStream_t st, LaunchedV
     return err != hipSuccess ? err : launched ? hipSuccess : hipErrorInvalidValue;
 }
 
-#define EFFORT_GEOMS(X) X(16, 1) X(16, 2) X(16, 4) X(8, 1) X(8, 2) X(8, 4) X(4, 1) X(4, 2) X(4, 4) X(2, 4)
-
 // Lets every instantiation of the kernel ask for up to the whole LDS of a CU as dynamic shared memory, on the CURRENT device.
-// Done once per device when its first context is created (api.hip), not lazily at launch: a function attribute belongs to a
+// Done once per device when its first context is created (ctx.hip), not lazily at launch: a function attribute belongs to a
 // device, launches may come from several threads and devices, and a launch may sit inside a hipGraph capture.
 hipError_t bucket_mul_prepare_device() {
     auto set = [](auto kernel, bool, bool, bool) -> hipError_t {            // (the kernel's static words come out of the same 160 KB)

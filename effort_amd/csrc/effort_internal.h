@@ -55,6 +55,8 @@ struct OutlierIndex {
 #endif
 constexpr int kMaxGroup = EFFORT_MAX_GROUP;        // calls per launch (the macro: A/B builds of the kernel-argument size, tools/ only)
 constexpr int kMaxGeoms = 4;
+// The (waves per workgroup, columns per lane) pairs the multiply kernel is built for: bucket_mul.hip instantiates them, plan.hip's supported() answers from them.
+#define EFFORT_GEOMS(X) X(16, 1) X(16, 2) X(16, 4) X(8, 1) X(8, 2) X(8, 4) X(4, 1) X(4, 2) X(4, 4) X(2, 4)
 constexpr int kQueueWords = 11 * 16;               // layout of GroupKArgs::queue (words)
 constexpr int kTraceOff = 512, kTraceItems = 4096;   // per-item trace records: u64 index into the stamp buffer / capacity         // distinct (shape, slicing) geometries per launch
 enum Prologue : uint16_t { kPreNone = 0, kPreSiluGate = 1, kPreRmsNorm = 2 };

@@ -1,6 +1,6 @@
 // The lane scheduler: which lane of a context a multiply launch goes to, which lanes it must follow, when the lanes are joined and when a
 // chain of dependent launches changes lanes -- as a host-only unit of plain data: no stream, no event, no HIP runtime call, no context, no
-// environment.  api.hip asks (capture rule, full?, pick), issues the HIP calls the answers call for, and reports back (commit, join);
+// environment.  ctx.hip asks (capture rule, full?, pick), issues the HIP calls the answers call for, and reports back (commit, join);
 // effort_debug_lanes (include/effort_hip_debug.h) plays a script of operations through a fresh book without a device.
 //
 // The rules.  A launch may run beside the launches in flight on the OTHER lanes unless it reads or writes what one of them writes, or writes

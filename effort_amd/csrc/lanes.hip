@@ -99,7 +99,7 @@ uint32_t LaneBook::join() {
 
 using namespace effort;
 
-// The scheduler without a context: the sequence of api.hip's do_group / join_lanes with the HIP calls left out.
+// The scheduler without a context: the sequence of mul.hip's do_group and ctx.hip's join_lanes with the HIP calls left out.
 extern "C" int effort_debug_lanes(int lanes, int nOps, const int64_t* ops, int64_t nWords, int64_t* out) {
     if (lanes < 1 || lanes > kMaxLanes || nOps < 0 || !ops || !out) return EFFORT_ERR_ARG;
     LaneBook B;

@@ -1,5 +1,5 @@
 // The launch planner: the shape of a group's multiply launches as a PURE function of plain data -- no context, no weight handle,
-// no stream, no HIP runtime call, no environment.  api.hip gathers the inputs (do_group), plan.hip decides, api.hip copies the
+// no stream, no HIP runtime call, no environment.  mul.hip gathers the inputs (do_group), plan.hip decides, mul.hip copies the
 // plan and the pointers into the launch descriptor.  effort_debug_plan (include/effort_hip_debug.h) runs it without a device.
 #pragma once
 #include "effort_internal.h"
@@ -14,7 +14,7 @@ struct PlanEnv {
     int persistent = -1;              // workgroups per CU of group launches: -1 heuristic, 0 plain grid, R > 0 persistent
     int tuneW = 0, tuneE = 0, tuneS = 0;      // tuning overrides (0 = heuristic)
     bool splitCutoff = false, clock = false;
-    uint32_t ablate = 0;              // lab switches (EFFORT_LAB builds: read from the environment by api.hip)
+    uint32_t ablate = 0;              // lab switches (EFFORT_LAB builds: read from the environment by mul.hip)
     bool noJobs = false, noCompact = false;
     size_t slabBytes = 0;             // a lane's scratch: partial tiles, arrival tickets, per-slice counts
     uint32_t maxTiles = 0, maxSlices = 0;

@@ -35,9 +35,10 @@ static bool fits_one_round(const PlanEnv& env, int n, uint32_t tiles, uint32_t a
 }
 
 bool supported(int W, int E) {
-    // must match EFFORT_GEOMS in bucket_mul.hip
-    return (W == 16 && (E == 1 || E == 2 || E == 4)) || (W == 8 && (E == 1 || E == 2 || E == 4)) ||
-           (W == 4 && (E == 1 || E == 2 || E == 4)) || (W == 2 && E == 4);
+#define EFFORT_CASE(w, e) if (W == w && E == e) return true;
+    EFFORT_GEOMS(EFFORT_CASE)
+#undef EFFORT_CASE
+    return false;
 }
 
 // Row slices per call when the launch carries `groupSize` calls and a lane owns E columns.  Measured on MI355X

@@ -34,7 +34,7 @@
 
 namespace effort {
 
-constexpr int kPrefillMaxRows = 64;       // == EFFORT_PREFILL_MAX_ROWS (api.hip asserts it)
+constexpr int kPrefillMaxRows = 64;       // == EFFORT_PREFILL_MAX_ROWS (glue.hip asserts it)
 constexpr int kPfWaves = 4;               // waves per workgroup: one 16-row tile of W each
 constexpr uint32_t kPfStage = 256;        // k elements per stage: 8 16-byte weight loads per lane
 constexpr int kPfChunks = kPfStage / 64;  // 64-element chunks (128-byte lines of a row) per stage

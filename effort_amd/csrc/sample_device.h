@@ -1,5 +1,5 @@
 // The sampled pick's random source: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), ONE definition
-// for the kernel (sample.hip) and for the host (effort_sample_bits in api.hip: what lets a test without a GPU pin the generator).
+// for the kernel (sample.hip) and for the host (effort_sample_bits in glue.hip: what lets a test without a GPU pin the generator).
 #pragma once
 #include <stdint.h>
 

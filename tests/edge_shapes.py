@@ -2,7 +2,7 @@
 TEST INFRASTRUCTURE: numpy only (no torch, no project code), so that the GPU test (tests/test_gpu_edge_shapes.py) and the planner's
 CPU test (tests/test_plan_domain_cpu.py) read ONE list.
 
-Registration (csrc/api.hip: check_bundle) takes any inDim in 4096 .. 65535, odd ones included, any outDim that is a multiple of 32 up to
+Registration (csrc/weights.hip: check_bundle) takes any inDim in 4096 .. 65535, odd ones included, any outDim that is a multiple of 32 up to
 16384, any percentLoad 1 .. 16, and any stack whose per-row arrays stay below 4 GiB.  The converters reach a small part of that
 (effort_convert_fp16: 4096 % outDim == 0 or outDim >= 4096, inDim <= 32000), but the multiply does not care where a layout came from:
 the bundles are built directly, as tests/test_gpu_parity.py::test_q4_outlier_tables builds its Q4 bundle.

@@ -101,7 +101,7 @@ def test_null_arguments_are_reported_not_crashed(hip_lib_built):
     assert lib.effort_last_error(None) == b"null context"
 
 
-# ---- registration bounds every per-row array of a stack (csrc/api.hip: check_bundle) -------------------------------------------------
+# ---- registration bounds every per-row array of a stack (csrc/weights.hip: check_bundle) -------------------------------------------------
 # The multiply reaches the buckets, the stats (8 bytes a bucket row) and the compact means (2 bytes) through 32-bit descriptors and byte
 # offsets.  Where a bucket row is shorter than 8 bytes -- FP16 outDim 32 (4 bytes); Q4 outDim 32, 64, 96 (2, 4, 6 bytes) -- the stats are
 # the larger array, and a stack whose buckets stay below 4 GiB can hold stats past it: such a handle used to be accepted, its
@@ -170,18 +170,25 @@ def test_registration_refuses_oversized_stats_before_reading(hip_lib_built):
 
 def test_shipped_library_reads_no_environment(hip_lib_built):
     """The A/B switches of the lab builds (-DEFFORT_LAB: EFFORT_ABLATE, EFFORT_NO_CUTJOBS ...) are compiled out of the shipped
-    library: no EFFORT_* variable name is left in it, and no object of the call path imports getenv (the one import left
-    is rocPRIM's own ROCPRIM_USE_ATOMIC_BLOCK_ID inside the offline Q4 converter's radix sort, convert_q4.o)."""
+    library: no EFFORT_* variable name is left in it, and no object the library is linked from imports getenv.  The objects are the
+    Makefile's SRCS, every one of them, so a new translation unit is covered the day it is added.  The one exception is convert_q4.o:
+    its import is rocPRIM's own ROCPRIM_USE_ATOMIC_BLOCK_ID inside the offline Q4 converter's radix sort."""
     import subprocess
     blob = open(hip_lib_built, "rb").read()
     for knob in (b"EFFORT_ABLATE", b"EFFORT_NO_CUTJOBS", b"EFFORT_NO_COMPACT_MEANS", b"EFFORT_TAIL_CALLS", b"EFFORT_TAIL_MULT"):
         assert knob not in blob, knob
     csrc = os.path.join(ROOT, "effort_amd", "csrc")
-    for obj in ("api.o", "plan.o", "lanes.o", "bucket_mul.o", "cutoff.o", "dispatch.o", "decode.o", "gemv.o", "convert.o", "comm.o"):
+    srcs = re.search(r"^SRCS\s*=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    objs = [s[:-len(".hip")] + ".o" for s in srcs if s.endswith(".hip")]
+    assert objs and len(objs) == len(srcs), srcs
+    for must in ("ctx.o", "weights.o", "comm.o", "mul.o", "glue.o", "plan.o", "lanes.o", "bucket_mul.o", "cutoff.o", "dispatch.o", "decode.o", "gemv.o",
+                 "convert.o", "prefill.o", "sample.o", "attention_block.o", "convert_q4.o"):
+        assert must in objs, must
+    for obj in objs:
         path = os.path.join(csrc, obj)
-        if os.path.exists(path):
-            syms = subprocess.run(["nm", "--undefined-only", path], capture_output=True, text=True, check=True).stdout
-            assert "getenv" not in syms, obj
+        assert os.path.exists(path), obj + ": every object of SRCS is there after a build (make -C effort_amd/csrc)"
+        syms = subprocess.run(["nm", "--undefined-only", path], capture_output=True, text=True, check=True).stdout
+        assert ("getenv" in syms) == (obj == "convert_q4.o"), obj
 
 
 def _multiply_kernel_disassembly(lib_path, tmp_path):

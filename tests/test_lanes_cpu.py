@@ -3,7 +3,7 @@ machine without a GPU: the hook needs no context and no device.
 
 (a) literal cases, derived by hand from the rules (lanes.h; DESIGN 4.2), on four lanes;
 (b) tests/golden/lane_table.json: every field the hook reports over the scripts of (a) and seeded random ones.  The table was recorded
-    from the scheduler as it was MOVED out of api.hip, before any simplification, and is never regenerated from later code: a rule edit
+    from the scheduler as it was MOVED out of api.hip (the host layer, since split: its executor is ctx.hip), before any simplification, and is never regenerated from later code: a rule edit
     shows here as a diff of the operations it moves, and the table changes only together with the rule;
 (c) the ordering property, which needs no recording: under a happens-before model of the streams, every launch is ordered after every
     earlier launch it conflicts with (RAW, WAW or WAR on overlapping ranges), and a join orders the context's stream after everything.

@@ -3,7 +3,7 @@ context and no device.
 
 (a) the slice counts tests/test_gpu_parity.py::test_geometry_rules_of_round_six asserts on hardware, as literals (256 CUs);
 (b) tests/golden/plan_table.json: every output of the hook over formats x lanes x CUs x thin / normal effort x group shapes.  The table was
-    recorded from the planner as it was MOVED out of api.hip, before any simplification, and is never regenerated from later code: a
+    recorded from the planner as it was MOVED out of api.hip (the host layer, since split: its caller is mul.hip), before any simplification, and is never regenerated from later code: a
     rule edit that moves a case shows here as a diff of that case, and the table changes only together with the rule, by hand or
     by a run of the parent's library.
 """

@@ -17,7 +17,7 @@ import pytest
 from tests import edge_shapes as es
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAX_TILES, MAX_SLICES, SLAB_BYTES = 1024, 4096, 64 << 20          # a lane's scratch (csrc/api.hip: effort_ctx)
+MAX_TILES, MAX_SLICES, SLAB_BYTES = 1024, 4096, 64 << 20          # a lane's scratch (csrc/host.h: effort_ctx)
 
 
 @pytest.fixture(scope="module")

@@ -3,6 +3,7 @@
 #include <rocblas/rocblas.h>
 
 #include "host.h"
+#include "prefill.h"
 #include "sample_device.h"
 
 using namespace effort;
@@ -169,6 +170,77 @@ extern "C" int effort_dense_gemm_rows_routed(effort_ctx* c, const void* W, int n
     OK_TRY(c->d_routedGroups.grow(c, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words()));
     return HIP_RC(c, launch_dense_gemm_rows_routed(static_cast<const uint16_t*>(W), (uint32_t)numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted.buf,
                                              c->d_routedPart.buf, c->d_routedGroups.buf, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows, c->stream));
+}
+// ---- the block multiplies on the bucketed weights (prefill_buckets.hip): no f16 core is read.
+// What a handle must be before it is looked at: FP16 (else EFFORT_ERR_KIND), percentLoad 16, no column shard, inDim % 32 == 0.
+static int bucket_handle_shape(const effort_w* w, const char* name) {
+    char what[128];
+    if (w->fmt != kFp16) { snprintf(what, sizeof(what), "%s: an FP16 bundle (Q4 buckets hold no whole matrix)", name); return fail(w->ctx, EFFORT_ERR_KIND, what); }
+    if (w->rowsPerIn != 16u || w->view || w->inDim % 32u || !bucket_gemm_rows_supported(w->inDim, w->outDim)) {
+        snprintf(what, sizeof(what), "%s: percentLoad 16, a full handle (no column shard), inDim %% 32 == 0", name);
+        return fail(w->ctx, EFFORT_ERR_SHAPE, what);
+    }
+    return EFFORT_OK;
+}
+// The handle's answer to "un-bucketable?", computed on first use (one kernel over the buckets; synchronises) and kept until a refresh.
+static int bucket_dense_state(const effort_w* w, int* ok) {
+    effort_ctx* c = w->ctx;
+    if (w->bucketDense < 0) {
+        int bad = 0;
+        hipSetDevice(c->device);
+        JOIN_TRY(c);
+        HIP_TRY(c, hipMemsetAsync(c->d_status + 2, 0, 4, c->stream));
+        HIP_TRY(c, launch_bucket_dense_check(w->buckets, w->rowPitch, w->cols, w->inDim, w->numExperts, c->d_status + 2, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&bad, c->d_status + 2, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        w->bucketDense = bad ? 0 : 1;
+    }
+    *ok = w->bucketDense;
+    return EFFORT_OK;
+}
+extern "C" int effort_weights_bucket_dense_ok(effort_w* w, int* host_out) {
+    if (!w || !w->ctx || w->dead || !host_out) return EFFORT_ERR_ARG;
+    OK_TRY(bucket_handle_shape(w, "weights_bucket_dense_ok"));
+    return bucket_dense_state(w, host_out);
+}
+static int bucket_refuse_collisions(effort_ctx* c, const effort_w* w, const char* name) {
+    int ok = 0;
+    OK_TRY(bucket_dense_state(w, &ok));
+    if (ok) return EFFORT_OK;
+    char what[160];
+    snprintf(what, sizeof(what), "%s: the bundle is not un-bucketable (two entries of one bucket name the same output: effort_convert_status reported drops)", name);
+    return fail(c, EFFORT_ERR_CONVERT, what);
+}
+extern "C" int effort_bucket_gemm_rows(effort_ctx* c, const effort_w* w, int expert, const float* x, float* out, int rows) {
+    if (!w || w->dead) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows: null handle");
+    if (!prefill_rows_ok(rows) || expert < 0 || (uint32_t)expert >= w->numExperts) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows: 1 <= rows <= 64, 0 <= expert < numExperts");
+    OK_TRY(bucket_handle_shape(w, "bucket_gemm_rows"));
+    if (!c || c != w->ctx || !x || !out) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows: null argument (or a handle of another context)");
+    JOIN_TRY(c);
+    OK_TRY(bucket_refuse_collisions(c, w, "bucket_gemm_rows"));
+    // effort_dense_gemm_rows's scratch, the same sizes: both calls are eager on the context's stream, neither outlives its launches' reads
+    OK_TRY(c->d_xhRows.grow(c, (size_t)rows * w->inDim, (size_t)EFFORT_PREFILL_MAX_ROWS * w->inDim));
+    OK_TRY(c->d_gemmPart.grow(c, dense_gemm_rows_partial_floats(w->inDim, w->outDim, (uint32_t)rows),
+                              dense_gemm_rows_partial_floats(w->inDim, w->outDim, EFFORT_PREFILL_MAX_ROWS)));
+    const uint16_t* B = reinterpret_cast<const uint16_t*>(reinterpret_cast<const unsigned char*>(w->buckets) + (size_t)expert * 16u * w->inDim * w->rowPitch);
+    return HIP_RC(c, launch_bucket_gemm_rows(B, w->rowPitch, x, c->d_xhRows.buf, c->d_gemmPart.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
+}
+extern "C" int effort_bucket_gemm_rows_routed(effort_ctx* c, const effort_w* w, const uint32_t* idx2, const float* x, int xPerSlot, float* out, int rows) {
+    if (!w || w->dead) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows_routed: null handle");
+    if (!prefill_rows_ok(rows) || (xPerSlot != 0 && xPerSlot != 1)) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows_routed: 1 <= rows <= 64, xPerSlot 0 / 1");
+    OK_TRY(bucket_handle_shape(w, "bucket_gemm_rows_routed"));
+    if (w->numExperts > 64u) return fail(c, EFFORT_ERR_SHAPE, "bucket_gemm_rows_routed: numExperts <= 64");
+    if (!c || c != w->ctx || !idx2 || !x || !out) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows_routed: null argument (or a handle of another context)");
+    JOIN_TRY(c);
+    OK_TRY(bucket_refuse_collisions(c, w, "bucket_gemm_rows_routed"));
+    // effort_dense_gemm_rows_routed's scratch, the same sizes
+    const size_t xRows = (size_t)(xPerSlot ? 2 : 1) * rows;
+    OK_TRY(c->d_xhRouted.grow(c, xRows * w->inDim, (size_t)2 * EFFORT_PREFILL_MAX_ROWS * w->inDim));
+    OK_TRY(c->d_routedPart.grow(c, dense_gemm_rows_routed_partial_floats(w->inDim, w->outDim, (uint32_t)rows),
+                                dense_gemm_rows_routed_partial_floats(w->inDim, w->outDim, EFFORT_PREFILL_MAX_ROWS)));
+    OK_TRY(c->d_routedGroups.grow(c, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words()));
+    return HIP_RC(c, launch_bucket_gemm_rows_routed(w->buckets, w->rowPitch, w->numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted.buf, c->d_routedPart.buf,
+                                              c->d_routedGroups.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
 }
 extern "C" int effort_moe_route_rows(effort_ctx* c, const float* h, const void* normW, const void* gateW, int n, int numExperts, float* gateOut,
                                      uint32_t* idx2, float* val2, int rows) {

@@ -108,6 +108,7 @@ struct effort_w {
     bool dead = false;                // effort_weights_free was called while views were alive: freed with the last of them
     float* rankBound = nullptr;       // [numExperts] fixed-point bound of the multiply (see launch_rank_bound)
     uint16_t* means16 = nullptr;      // FP16: the row means alone (stats lane .w), one u16 per bucket row (launch_compact_means)
+    mutable int bucketDense = -1;     // effort_weights_bucket_dense_ok: -1 not checked yet, 0 two entries collide, 1 un-bucketable (effort_weights_refresh: -1 again)
     // Q4 outliers
     uint64_t nOutliers = 0;
     uint32_t* olBlockPtr = nullptr;   // entry bounds per block of 64 outputs (a column shard's: a slice of the full handle's)

@@ -30,21 +30,16 @@
 // ascending stage, chunk, u order.  A token column that is not live is a zero operand (zeros are staged for it: no x row at or
 // beyond `rows` is read, nor the scratch's stale halves); a k step past inDim multiplies zeros.  So a row's bits are the same for
 // every `rows` and every position in the block.
-#include "effort_internal.h"
+#include "prefill.h"
 
 namespace effort {
 
-constexpr int kPrefillMaxRows = 64;       // == EFFORT_PREFILL_MAX_ROWS (glue.hip asserts it)
+// (kPrefillMaxRows, kPfStage, kPfKeepBytes and the k split are prefill.h's: the bucket kernel of prefill_buckets.hip shares them)
 constexpr int kPfWaves = 4;               // waves per workgroup: one 16-row tile of W each
-constexpr uint32_t kPfStage = 256;        // k elements per stage: 8 16-byte weight loads per lane
 constexpr int kPfChunks = kPfStage / 64;  // 64-element chunks (128-byte lines of a row) per stage
 constexpr uint32_t kPfQ = kPfStage / 8;   // 16-byte pieces of a token row per stage
 constexpr uint32_t kPfPitch = kPfStage / 8 + 1;   // uint4 per staged token row: 256 bytes + 16 of padding (a 256-byte pitch puts every token on the same banks)
 constexpr uint32_t kPfMaxSplits = 16, kPfTargetGroups = 256;
-constexpr size_t kPfKeepBytes = 64u << 20;   // == kGemvKeepBytes (gemv.hip): a larger matrix is streamed nt, for the reason given there
-
-typedef _Float16 pf_half8 __attribute__((ext_vector_type(8)));
-typedef float pf_f32x4 __attribute__((ext_vector_type(4)));
 
 // x.asFloat16() (mps.swift:19) of the live rows, once per call
 __global__ void rows_to_f16_kernel(const float* __restrict__ x, uint16_t* __restrict__ xh, uint32_t n) {
@@ -62,8 +57,7 @@ __global__ void reduce_splits_kernel(const float* __restrict__ part, float* __re
 }
 
 // The k split of a shape: stages per split and the number of splits (a function of the shape alone -- never of rows).
-struct PfSplit { uint32_t per, splits; };
-static PfSplit pf_split(uint32_t inDim, uint32_t outDim) {
+PfSplit pf_split(uint32_t inDim, uint32_t outDim) {
     const uint32_t stages = (inDim + kPfStage - 1u) / kPfStage, groups = (outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves);
     uint32_t want = (kPfTargetGroups + groups - 1u) / groups;
     if (want > kPfMaxSplits) want = kPfMaxSplits;
@@ -181,8 +175,7 @@ __global__ __launch_bounds__(64 * kPfWaves, 2) void dense_gemm_rows_kernel(const
 
 // ---- the routed front end: every assignment a = 2 r + s (token r, slot s) of a Mixtral block multiplies the expert it picked.
 // Assignments are grouped by expert ON THE DEVICE (the expert numbers never reach the host), in assignment order: cnt[e] and
-// list[e][0 .. cnt[e]).  kPfMaxAssign = 2 * kPrefillMaxRows entries per expert: duplicates or clamping can give one expert all of them.
-constexpr uint32_t kPfMaxAssign = 2u * kPrefillMaxRows, kPfMaxExperts = 64;
+// list[e][0 .. cnt[e]).  kPfMaxAssign = 2 * kPrefillMaxRows entries per expert (prefill.h).
 
 // The prologue of a routed call, ONE launch: blocks 0 .. gridDim.x - 2 write f16(x) (rows_to_f16_kernel's element each), the last block
 // groups.  Thread e of it walks the 2 * rows clamped expert numbers (LDS) in ascending a: deterministic, no atomics.
@@ -304,6 +297,21 @@ hipError_t launch_dense_gemm_rows_routed(const uint16_t* W, uint32_t numExperts,
     if (e != hipSuccess || sp.splits == 1u) return e;
     const uint32_t no = assigns * outDim;
     hipLaunchKernelGGL(reduce_splits_kernel, dim3((no + 255u) / 256u), dim3(256), 0, st, part, out, no, sp.splits);
+    return hipGetLastError();
+}
+
+// ---- the launches prefill_buckets.hip shares (prefill.h)
+hipError_t launch_rows_to_f16(const float* x, uint16_t* xh, uint32_t n, hipStream_t st) {
+    hipLaunchKernelGGL(rows_to_f16_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, x, xh, n);
+    return hipGetLastError();
+}
+hipError_t launch_reduce_splits(const float* part, float* out, uint32_t n, uint32_t splits, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, part, out, n, splits);
+    return hipGetLastError();
+}
+hipError_t launch_routed_prologue(const float* x, uint16_t* xh, uint32_t n, const uint32_t* idx2, uint32_t assigns, uint32_t numExperts, uint32_t* cnt,
+                                  uint32_t* list, hipStream_t st) {
+    hipLaunchKernelGGL(routed_prologue_kernel, dim3((n + 255u) / 256u + 1u), dim3(256), 0, st, x, xh, n, idx2, assigns, numExperts, cnt, list);
     return hipGetLastError();
 }
 

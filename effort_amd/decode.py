@@ -510,7 +510,20 @@ class Decoder:
             return
         g.check(rc, "dense_gemm_rows_routed")
 
-    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense"):
+    def _bucket_rows(self, x, ew, out, rows: int):
+        """out[r] = U * f16(x[r]) for the first ``rows`` rows, U the un-bucketed matrix of ``ew`` (effort_bucket_gemm_rows): no core is
+        read.  No fallback: every refusal of the library was ruled out by ``prefill`` before anything was enqueued, so one is an error."""
+        g = self.g
+        g.check(_lib.lib().effort_bucket_gemm_rows(g.ctx, ew.handle, 0, _p(x), _p(out), rows), "bucket_gemm_rows")
+
+    def _bucket_rows_routed(self, x, ew, idx2, out, rows: int, per_slot: bool):
+        """``_gemm_rows_routed`` on the un-bucketed expert stack of ``ew`` (effort_bucket_gemm_rows_routed); no fallback either."""
+        g = self.g
+        g.check(_lib.lib().effort_bucket_gemm_rows_routed(g.ctx, ew.handle, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), rows),
+                "bucket_gemm_rows_routed")
+
+    def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense",
+                weights: str = "cores"):
         """Ingest prompt tokens in bulk: fill ``kCache`` / ``vCache`` rows ``pos0 .. pos0 + T - 1`` of every layer, in blocks of at most
         ``chunk`` (<= 64) tokens that share ONE pass over each matrix, then set ``pos`` to ``pos0 + T``.  No logits, no pick: the next
         ``token_step`` (or graph replay) continues from the caches.  Eager, never captured: ``pos0`` and the block sizes are host values.
@@ -535,7 +548,18 @@ class Decoder:
         pending afterwards.  Still the dense arithmetic, still chunk-independent bits (a routed product is the block multiply's for
         that token alone).  The last block's routing stays in ``pf_gateIdxs[layer][row]`` / ``pf_gateOut[layer][row]``.
 
-        Raises ValueError, before anything is enqueued: a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
+        ``weights``: ``"cores"``, the default, is the walk above on every bundle's f16 core.  ``"buckets"`` multiplies by the bucketed
+        weights instead, un-bucketed on the fly (effort_bucket_gemm_rows / effort_bucket_gemm_rows_routed): no core is looked at, so a
+        model made with ``keep_cores=False`` -- half the memory -- prefills.  It needs every bundle FP16 with its buckets loaded,
+        ``percentLoad`` 16 and un-bucketable (``ExpertWeights.unbucket``: no two entries of a bucket name the same output; asked of the
+        library once per handle), and serves ``ffn="dense"`` and ``ffn="routed"`` alike.  The matrix it multiplies is the core with the
+        low four mantissa bits of every weight replaced by its position in the bucket: the caches hold the K / V a decode at effort
+        1.0 would write (up to the order of the sums and the f16 rounding of the inputs), not the dense path's -- bit for bit those of
+        ``weights="cores"`` on a model whose cores are ``unbucket()`` of its buckets.  There is no row-by-row fallback: no core exists
+        to fall back to.
+
+        Raises ValueError, before anything is enqueued: a ``weights`` other than ``"cores"`` / ``"buckets"``; under ``"buckets"`` a Q4
+        or core-only bundle, a bundle truncated below ``percentLoad`` 16 and one that is not un-bucketable; a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
         ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"``, an ``ffn`` other
         than ``"dense"`` / ``"routed"``."""
@@ -544,16 +568,26 @@ class Decoder:
         T = len(ids)
         if ffn not in ("dense", "routed"):
             raise ValueError(f"Decoder.prefill: ffn must be 'dense' or 'routed', not {ffn!r}")
-        routed = ffn == "routed"
+        if weights not in ("cores", "buckets"):
+            raise ValueError(f"Decoder.prefill: weights must be 'cores' or 'buckets', not {weights!r}")
+        routed, from_buckets = ffn == "routed", weights == "buckets"
         if routed and not (cfg.numExperts >= 2 and all(L.ffnGate is not None and L.ffnGate.dtype == torch.float16 for L in m.layers)):
             raise ValueError("Decoder.prefill: ffn='routed' is for Mixtral models (an f16 ffnGate in every layer, numExperts >= 2)")
         if not routed and (self.moe or cfg.numExperts > 1):
             raise ValueError("Decoder.prefill: dense-FFN models only (a Mixtral layer routes per token)")
         if self.sharded:
             raise ValueError("Decoder.prefill: not implemented for the column-sharded decode loop")
-        if any(getattr(L, w).core is None for L in m.layers for w in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")):
+        bundles = [getattr(L, w) for L in m.layers for w in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")]
+        if from_buckets:
+            if any(ew.q4 or not ew.bucketsLoaded for ew in bundles):
+                raise ValueError("Decoder.prefill: weights='buckets' needs every bundle FP16 with its buckets loaded (not a Q4 or core-only bundle)")
+            if any(ew.percentLoad != 16 for ew in bundles):
+                raise ValueError("Decoder.prefill: weights='buckets' needs percentLoad 16 (a truncated bundle does not hold the whole matrix)")
+            if routed and any(getattr(L, w).numExperts != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
+                raise ValueError("Decoder.prefill: ffn='routed' needs the expert stacks [numExperts] (w1, w2, w3)")
+        elif any(ew.core is None for ew in bundles):
             raise ValueError("Decoder.prefill: every bundle needs its f16 core (Model.random(keep_cores=True), or a Q4 model)")
-        if routed and any(getattr(L, w).core.dim() != 3 or int(getattr(L, w).core.shape[0]) != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
+        if routed and not from_buckets and any(getattr(L, w).core.dim() != 3 or int(getattr(L, w).core.shape[0]) != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
             raise ValueError("Decoder.prefill: ffn='routed' needs the expert stacks' cores [numExperts, out, in] (Model.random(keep_cores=True))")
         if not 1 <= chunk <= self.PREFILL_MAX_ROWS:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
@@ -564,9 +598,22 @@ class Decoder:
         attend, attendName = ((lib.effort_attention_rows, "attention_rows") if attention == "rows" else
                               (lib.effort_attention_block, "attention_block"))
         g._bind_stream()
+        if from_buckets:                                   # (the last refusal: the library looks at each handle's buckets once and remembers)
+            for ew in bundles:
+                ok = C.c_int(0)
+                g.check(lib.effort_weights_bucket_dense_ok(ew.handle, C.byref(ok)), "weights_bucket_dense_ok")
+                if not ok.value:
+                    raise ValueError("Decoder.prefill: weights='buckets' needs un-bucketable bundles (two entries of one bucket name the same output: "
+                                     "the converter reported drops)")
         self._prefill_buffers(chunk)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
         rope = C.c_float(cfg.ropeBase)
+        if from_buckets:
+            mul = lambda x, ew, out, rows: self._bucket_rows(x, ew, out, rows)                             # noqa: E731
+            mul_routed = lambda x, ew, idx2, out, rows, per_slot: self._bucket_rows_routed(x, ew, idx2, out, rows, per_slot)   # noqa: E731
+        else:
+            mul = lambda x, ew, out, rows: self._gemm_rows(x, ew.core, out, rows)                          # noqa: E731
+            mul_routed = lambda x, ew, idx2, out, rows, per_slot: self._gemm_rows_routed(x, ew.core, idx2, out, rows, per_slot)   # noqa: E731
         for b0 in range(0, T, chunk):
             rows, p = min(chunk, T - b0), pos0 + b0
             self.pf_ids[:rows].copy_(torch.tensor(ids[b0:b0 + rows], dtype=torch.int32))
@@ -576,29 +623,29 @@ class Decoder:
                 kc, vc = _p(self.kCache[n]), _p(self.vCache[n])
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(delta), _p(L.attnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 for ew, out in ((L.wq, self.pf_xq_temp), (L.wk, self.pf_xk_temp), (L.wv, self.pf_xv_temp)):
-                    self._gemm_rows(self.pf_norm, ew.core, out, rows)
+                    mul(self.pf_norm, ew, out, rows)
                 ck(lib.effort_rope_kv_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
                                            cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
                 if n == len(m.layers) - 1:
                     break                                  # nothing after the last layer's cache write reaches a cache
                 ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim, self.maxTokens), attendName)
-                self._gemm_rows(self.pf_attnOutput, L.wo.core, self.pf_attnFfnOut, rows)
+                mul(self.pf_attnOutput, L.wo, self.pf_attnFfnOut, rows)
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 if routed:
                     idx2 = self.pf_gateIdxs[n]
                     ck(lib.effort_moe_route_rows(g.ctx, _p(self.pf_h), _p(L.ffnNorm), _p(L.ffnGate), cfg.stateDim, cfg.numExperts, _p(self.pf_gateOut[n]),
                                                  _p(idx2), _p(self.pf_gateVals), rows), "moe_route_rows")
-                    self._gemm_rows_routed(self.pf_norm, L.w1.core, idx2, self.pf_x1r, rows, False)
-                    self._gemm_rows_routed(self.pf_norm, L.w3.core, idx2, self.pf_x3r, rows, False)
+                    mul_routed(self.pf_norm, L.w1, idx2, self.pf_x1r, rows, False)
+                    mul_routed(self.pf_norm, L.w3, idx2, self.pf_x3r, rows, False)
                     ck(lib.effort_silu_mul(g.ctx, _p(self.pf_x1r), _p(self.pf_x3r), _p(self.pf_x2r), rows * 2 * cfg.hiddenDim), "silu")
-                    self._gemm_rows_routed(self.pf_x2r, L.w2.core, idx2, self.pf_ffnOutR, rows, True)
+                    mul_routed(self.pf_x2r, L.w2, idx2, self.pf_ffnOutR, rows, True)
                     ck(lib.effort_mix2_add_rows(g.ctx, _p(self.pf_h), _p(self.pf_ffnOutR), _p(self.pf_gateVals), cfg.stateDim, rows), "mix2_add_rows")
                     delta = None                           # the mix landed on h
                     continue
-                self._gemm_rows(self.pf_norm, L.w1.core, self.pf_x1, rows)
-                self._gemm_rows(self.pf_norm, L.w3.core, self.pf_x3, rows)
+                mul(self.pf_norm, L.w1, self.pf_x1, rows)
+                mul(self.pf_norm, L.w3, self.pf_x3, rows)
                 ck(lib.effort_silu_mul(g.ctx, _p(self.pf_x1), _p(self.pf_x3), _p(self.pf_x2), rows * cfg.hiddenDim), "silu")
-                self._gemm_rows(self.pf_x2, L.w2.core, self.pf_ffnOut, rows)
+                mul(self.pf_x2, L.w2, self.pf_ffnOut, rows)
                 delta = self.pf_ffnOut
         self.pos.fill_(pos0 + T)
 
@@ -633,7 +680,7 @@ class Decoder:
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
             collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64,
-            prefill_attention: str = "rows", prefill_ffn: str = "dense"):
+            prefill_attention: str = "rows", prefill_ffn: str = "dense", prefill_weights: str = "cores"):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
@@ -644,7 +691,8 @@ class Decoder:
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
         ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
-        ``"routed"``: a Mixtral prompt prefills only with ``"routed"``).
+        ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"``: a
+        model without cores prefills only with ``"buckets"``, and its caches then hold effort-1.0 K / V, not dense ones).
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
@@ -660,7 +708,7 @@ class Decoder:
         if skip:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn)
+            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn, prefill_weights)
             torch.cuda.synchronize()
             self.last_prefill_s = time.perf_counter() - tp
         for step in range(skip, numTokens):

@@ -19,6 +19,42 @@ def _ptr(t: torch.Tensor | None):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def unbucket(buckets: torch.Tensor, inSize: int, outSize: int) -> torch.Tensor:
+    """The UN-BUCKETED matrix U of FP16 buckets at ``percentLoad`` 16 -- f16 [E, outSize, inSize] -- in torch ops, on the host or the
+    device the buckets live on.  ``buckets`` is [E, 16 * inSize, cols] (or one expert's [16 * inSize, cols]) of 16-bit words, dense or
+    a strided view of pitched storage: only the ``cols = outSize / 16`` payload words of a row are read, the padding is ignored.
+
+    For expert e, input j, bucket column c and rank r let w = buckets[e][r * inSize + j][c].  w == 0x0000 is skipped; otherwise
+    U[e][16 c + (w & 15)][j] = w: the position bits stay in the value, exactly as bucketMul multiplies them.  Elements no entry names
+    are +0.  Raises ValueError when two non-skipped entries of one (e, j, c) name the same position (the converter's literal
+    preBucketize path can write that; ``effort_convert_status`` reports drops then): such a bundle holds no matrix to return.
+
+    This is the specification of what ``Decoder.prefill(weights="buckets")`` multiplies by, and the way back from a bucket file
+    written without cores: U is the core with the low four mantissa bits of every weight replaced by its position."""
+    inSize, outSize = int(inSize), int(outSize)
+    if buckets.element_size() != 2:
+        raise ValueError("unbucket: buckets of 16-bit words")
+    b = buckets.view(torch.int16)
+    if b.dim() == 2:
+        b = b.unsqueeze(0)
+    cols = outSize // 16
+    if outSize % 16 or b.dim() != 3 or b.shape[1] != 16 * inSize or b.shape[2] < cols:
+        raise ValueError(f"unbucket: buckets [E, {16 * inSize}, >= {cols}] expected (percentLoad 16), got {tuple(b.shape)}")
+    out = torch.empty((b.shape[0], outSize, inSize), dtype=torch.int16, device=b.device)
+    for e in range(b.shape[0]):                                # (an expert at a time: the scatter works on 4-byte words)
+        w = b[e, :, :cols].reshape(16, inSize, cols).to(torch.int32) & 0xFFFF
+        w = w.permute(1, 2, 0).contiguous()                    # [j][c][rank]
+        pos = (w & 15).to(torch.int64)
+        named = torch.zeros((inSize, cols, 16), dtype=torch.int32, device=b.device).scatter_add_(2, pos, (w != 0).to(torch.int32))
+        if bool((named > 1).any()):
+            raise ValueError("unbucket: two entries of one bucket name the same output position -- the bundle is not un-bucketable")
+        # (no two non-zero entries share a slot, and a skipped entry adds 0: the sum IS the entry)
+        u = torch.zeros((inSize, cols, 16), dtype=torch.int32, device=b.device).scatter_add_(2, pos, w)
+        u = ((u ^ 0x8000) - 0x8000).to(torch.int16)            # the 16-bit pattern as int16
+        out[e] = u.reshape(inSize, outSize).t()
+    return out.view(torch.float16)
+
+
 class ExpertWeights:
     def __init__(self, buckets: torch.Tensor, stats: torch.Tensor, probes: torch.Tensor, inSize: int, outSize: int,
                  percentLoad: int | None = None, numExperts: int = 1, outliers: torch.Tensor | None = None,
@@ -151,6 +187,13 @@ class ExpertWeights:
         rows = self.inSize * percentLoad
         return ExpertWeights(self.buckets[:, :rows].contiguous(), self.stats[:, :rows].contiguous(), self.probes,
                              self.inSize, self.outSize, percentLoad, self.numExperts, core=self.core)
+
+    def unbucket(self) -> torch.Tensor:
+        """``unbucket`` of this bundle's buckets: f16 [numExperts, outSize, inSize], the matrix ``Decoder.prefill(weights="buckets")``
+        multiplies by.  FP16 bundles with their buckets loaded at ``percentLoad`` 16 only."""
+        if self.q4 or not self.bucketsLoaded or self.percentLoad != 16:
+            raise ValueError("ExpertWeights.unbucket: an FP16 bundle with its buckets loaded at percentLoad 16")
+        return unbucket(self.buckets, self.inSize, self.outSize)
 
     def align_rows(self) -> int:
         """For bundles held in the reference's dense layout (loaded from a file, ``from_core(aligned=False)``): give the handle

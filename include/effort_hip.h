@@ -359,7 +359,7 @@ EFFORT_API int effort_decode_status(effort_ctx* ctx, int* host_out);
  * CONTRACT: row r of out depends on row r of x and on W only -- not on rows, not on the other rows, not on r: its bits are the same
  * for every rows and every row position (the order of the sums over k is fixed).  Token columns past rows are zero operands: no x row
  * at or beyond rows is read, no out element at or beyond rows * outDim is written.  It agrees with effort_dense_gemv to rounding of
- * the f32 sums, not bit for bit (another order).  Uses context scratch of its own, shared with no other entry point: 64 * inDim halves
+ * the f32 sums, not bit for bit (another order).  Uses context scratch shared with effort_bucket_gemm_rows alone: 64 * inDim halves
  * for f16(x) and splits * 64 * outDim floats for the partial sums of its k split (splits <= 16, a function of the shape).  Both only
  * grow: a call that needs more than there is synchronises the stream, frees and allocates.  The entry point is meant to be called
  * eagerly.  A captured graph that holds it keeps the scratch addresses of its capture, so it stays valid only if no later call grows
@@ -381,12 +381,53 @@ EFFORT_API int effort_dense_gemm_rows(effort_ctx* ctx, const void* W_f16_dev, co
  * Shapes: one expert's (inDim, outDim) as effort_dense_gemm_rows serves them (ONE expert below 4 GiB: the stack may be larger),
  * numExperts <= 64; anything else returns EFFORT_ERR_SHAPE (the caller falls back to effort_dense_gemv_expert per assignment).
  * xPerSlot other than 0 / 1, numExperts < 1: EFFORT_ERR_ARG.  The weight stream is nt when ONE expert's matrix is above 64 MiB.
- * Uses context scratch of its own, shared with no other entry point: 128 * inDim halves for f16(x), splits * 128 * outDim floats for
+ * Uses context scratch shared with effort_bucket_gemm_rows_routed alone: 128 * inDim halves for f16(x), splits * 128 * outDim floats for
  * the partial sums of the k split, and 64 * 129 words for the groups.  The first two only grow, by effort_dense_gemm_rows's rule, and the
  * same advice holds before capturing.  Up to three launches: convert + group, multiply, and the reduce when the shape has more than
  * one split. */
 EFFORT_API int effort_dense_gemm_rows_routed(effort_ctx* ctx, const void* W_f16_dev, int numExperts, const uint32_t* idx2_dev, const float* x_dev,
                                   int xPerSlot, float* out_dev, int inDim, int outDim, int rows);
+/* ---- prefill straight from the bucketed weights: no f16 core ------------------------------------
+ * At percentLoad 16 an FP16 bundle's buckets hold the whole matrix, so the f16 core a prefill would read is a second copy.  These
+ * entry points multiply a block by the UN-BUCKETED matrix U of a registered handle, un-bucketing on the fly:
+ *   for expert e, input j, bucket column c and rank r let w be the 16-bit entry buckets[e][r * inDim + j][c].  w == 0x0000 is
+ *   skipped; otherwise U[e][16 c + (w & 15)][j] = w -- the position bits STAY in the value, exactly as bucketMul multiplies them
+ *   (bucketMul.metal:100-102); elements no entry names are +0.
+ * A bundle is UN-BUCKETABLE iff no two non-skipped entries of one (e, j, c) name the same position.  The converter's fast path
+ * always writes such bundles; its literal preBucketize path (zero padding of a non-power-of-two row, effort_convert_status reports
+ * drops) can write collisions, and those bundles are refused (EFFORT_ERR_CONVERT), never guessed at.
+ * U is the core with its low four mantissa bits replaced by positions: a prefill through these calls writes the K / V a decode at
+ * effort 1.0 would write (up to the order of the sums and the f16(x) rounding), NOT the dense path's K / V.
+ *
+ * effort_weights_bucket_dense_ok: *host_out = 1 when the handle is un-bucketable, 0 when not.  One small kernel over the buckets;
+ * synchronises.  The answer is cached on the handle; effort_weights_refresh clears it (the next call looks again).  The multiplies
+ * below run it themselves on a handle's first use.  EFFORT_ERR_KIND for a Q4 handle, EFFORT_ERR_SHAPE as below.
+ *
+ * effort_bucket_gemm_rows: out[r] = U[expert] * f16(x[r]) for r < rows, x f32 [rows][inDim], out f32 [rows][outDim].
+ * CONTRACT: BIT FOR BIT what effort_dense_gemm_rows writes when U[expert] is given to it as W (the same k split, the same order of
+ * the sums, the same operand slots on v_mfma_f32_16x16x32_f16, zero operands for dead token columns and for k past inDim); so that
+ * entry's contract holds here word for word -- row r of out depends on row r of x and on U alone, no x row at or beyond rows is
+ * read, nothing at or beyond rows * outDim is written.  A bucket row is read only inside its 2 * outDim / 16 payload bytes (the pitch
+ * padding may hold anything), other experts' buckets are not read, and any row pitch registration accepts is served.  The bucket
+ * stream is nt when one expert's matrix is above 64 MiB.
+ *
+ * effort_bucket_gemm_rows_routed: effort_dense_gemm_rows_routed on the handle's expert stack (numExperts, inDim, outDim are the
+ * handle's): out[a] = U[min(idx2_dev[a], numExperts - 1)] * f16(input of a), BIT FOR BIT what effort_bucket_gemm_rows writes for that
+ * input row and expert alone with rows = 1.  Expert e's bucket rows start at row 16 * inDim * e; an expert nobody picked is not read;
+ * an expert's columns are walked 64 at a time.
+ *
+ * Refusals, nothing enqueued on any of them, values before pointers: rows outside 1 .. 64, expert outside 0 .. numExperts - 1,
+ * xPerSlot other than 0 / 1, a NULL handle: EFFORT_ERR_ARG; a Q4 handle: EFFORT_ERR_KIND; percentLoad != 16, a column shard,
+ * inDim % 32 != 0, routed with numExperts > 64: EFFORT_ERR_SHAPE; then a NULL pointer (or a context other than the handle's):
+ * EFFORT_ERR_ARG; then, the lanes joined, a bundle that is not un-bucketable: EFFORT_ERR_CONVERT (on a handle's first use this runs
+ * the check, which writes a status word of the context and nothing else).
+ * SCRATCH: effort_bucket_gemm_rows uses effort_dense_gemm_rows's context scratch and effort_bucket_gemm_rows_routed uses
+ * effort_dense_gemm_rows_routed's (the sizes are the same; the calls are eager on one stream, so neither finds the other's data in
+ * use); the growth rule and the advice before capturing are those entries'.  Up to three launches each, as their core twins. */
+EFFORT_API int effort_weights_bucket_dense_ok(effort_w* w, int* host_out);
+EFFORT_API int effort_bucket_gemm_rows(effort_ctx* ctx, const effort_w* w, int expert, const float* x_dev, float* out_dev, int rows);
+EFFORT_API int effort_bucket_gemm_rows_routed(effort_ctx* ctx, const effort_w* w, const uint32_t* idx2_dev, const float* x_dev, int xPerSlot,
+                                   float* out_dev, int rows);
 /* Block forms of the Mixtral glue, per row BIT FOR BIT the token forms (the same body):
  * effort_moe_route_rows: effort_moe_route on row r of h [rows][n]; idx2 / val2 [rows][2], gate_out (may be NULL) [rows][numExperts].
  * effort_mix2_add_rows: effort_mix2_add on row r of h [rows][n] with f0 = f[r][0], f1 = f[r][1] (f f32 [rows][2][n]) and val2[r]. */

@@ -12,7 +12,8 @@ record also goes to profiles/r09_prefill.json; asked for alone, it skips the hea
 (effort_attention_rows beside effort_attention_block on rotating caches, and 256- and 2048-token prompts through `Decoder.prefill` on
 both attention paths; its record also goes to profiles/r10_prefill_attention.json; standalone like `decode_prefill`) and
 `prefill_mixtral` (a Mixtral prompt: the routed block multiply beside 8 dense block calls, and Decoder.prefill(ffn="routed") beside the
-token loop; its record also goes to profiles/r11_prefill_mixtral.json; standalone too).
+token loop; its record also goes to profiles/r11_prefill_mixtral.json; standalone too) and `prefill_buckets` (prefill straight from the
+bucketed weights beside the core kernel in the same run; its record also goes to profiles/r12_prefill_buckets.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -30,8 +31,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral")             # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets")             # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -650,6 +651,133 @@ def prefill_mixtral(b, res):
     del dec, model
 
 
+def prefill_buckets(b, res):
+    """Prefill straight from the bucketed weights (effort_bucket_gemm_rows: the block multiply un-bucketing on the fly) beside the core
+    kernel MEASURED IN THE SAME RUN.  Kernel legs, decode_prefill's protocol (rotating disjoint matrices, more than 768 MB of them per
+    shape and kernel, one pass per graph, best of 3 windows): us per call at 16 and 64 rows on the decode loop's four shapes, the core
+    leg on ``unbucket()`` of the same buckets.  Model legs, Mistral-7B shapes, a 256-token prompt: `Decoder.prefill` ms per prompt token
+    with ``weights="cores"`` and ``weights="buckets"`` (eager, synchronised wall time, best of 3), the cosine of the bucket-prefilled K
+    caches against the core-prefilled ones (the cores here are the DENSE ones: what the 4-bit perturbation of every weight costs), and
+    ``torch.cuda.memory_allocated`` for the model with its cores and after dropping them -- after which the prompt is prefilled once more."""
+    import ctypes as C
+    import gc
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    from effort_amd.weights import ExpertWeights
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(78)
+
+    def us_per_call(fn, calls):
+        g._bind_stream()
+        fn()                                                                     # (warm: the first bucket call of a handle runs its check, which synchronises)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            fn()
+        g._bind_stream()
+        for _ in range(3):
+            gr.replay()
+        torch.cuda.synchronize()
+        best = float("inf")
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
+        return best
+
+    kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events; both kernels in this run; "
+                        "a workgroup of the bucket kernel owns 32 bucket columns (64 bytes of every bucket row, 512 outputs)"}
+    for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
+        nbytes = outD * inD * 2
+        count = max(4, -(-(768 << 20) // nbytes))
+        ews = [ExpertWeights.from_core((torch.randn((outD, inD), generator=gen, device=b.dev, dtype=torch.float32) * 0.02).to(torch.float16))
+               for _ in range(count)]
+        for ew in ews:
+            ew.core = ew.unbucket()[0].contiguous()
+            ew.handle
+        x = torch.randn((64, inD), generator=gen, device=b.dev, dtype=torch.float32)
+        out = torch.zeros((64, outD), device=b.dev)
+
+        def cores(rows):
+            def fn():
+                g._bind_stream()
+                for ew in ews:
+                    g.check(lib.effort_dense_gemm_rows(g.ctx, p(ew.core), p(x), p(out), inD, outD, rows), "dense_gemm_rows")
+            return fn
+
+        def buckets(rows):
+            def fn():
+                g._bind_stream()
+                for ew in ews:
+                    g.check(lib.effort_bucket_gemm_rows(g.ctx, ew.handle, 0, p(x), p(out), rows), "bucket_gemm_rows")
+            return fn
+        row = {"matrices": count, "weight_bytes": nbytes, "bucket_row_pitch": ews[0].rowPitch}
+        for rows in (16, 64):
+            for name, fn in ((f"core_rows_{rows}", cores(rows)), (f"bucket_rows_{rows}", buckets(rows))):
+                us = us_per_call(fn, count)
+                row[name] = {"us_per_call": round(us, 2), "TBps_of_weight_bytes": round(nbytes / us / 1e6, 3)}
+            row[f"bucket_over_core_time_{rows}"] = round(row[f"bucket_rows_{rows}"]["us_per_call"] / row[f"core_rows_{rows}"]["us_per_call"], 3)
+        kern[f"{inD}->{outD}"] = row
+        del ews, x, out
+        gc.collect()
+        torch.cuda.empty_cache()
+    out = {"kernel": kern}
+
+    nprompt = 256
+    model = Model.random(MistralConfig(), seed=1)
+    torch.cuda.synchronize()
+    mem_with = torch.cuda.memory_allocated()
+    dec = Decoder(model, maxTokens=nprompt + 8)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+
+    def prefill(weights):
+        dec.prefill(prompt, weights=weights)                     # the warm call (and every handle's check); not timed
+        best = float("inf")
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dec.prefill(prompt, weights=weights)
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t0)
+        return round(best * 1e3 / nprompt, 4)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "prompt_tokens": nprompt,
+         "protocol": "eager, synchronised wall time of Decoder.prefill(chunk=64) over the whole prompt, best of 3 after a warm call"}
+    m["prefill_cores_ms_per_prompt_token"] = prefill("cores")
+    k_cores = [k[:nprompt].clone() for k in dec.kCache]
+    m["prefill_buckets_ms_per_prompt_token"] = prefill("buckets")
+    cos = [float(torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), k[:nprompt].double().reshape(1, -1))) for a, k in zip(k_cores, dec.kCache)]
+    m["k_cache_cosine_buckets_vs_dense_cores"] = {"first_layer": cos[0], "last_layer": cos[-1], "min": min(cos), "mean": sum(cos) / len(cos)}
+    m["buckets_over_cores_time"] = round(m["prefill_buckets_ms_per_prompt_token"] / m["prefill_cores_ms_per_prompt_token"], 3)
+    before = torch.cuda.memory_allocated()
+    for L in model.layers:
+        for w in ("wq", "wk", "wv", "wo", "w1", "w2", "w3"):
+            getattr(L, w).core = None
+    gc.collect()
+    torch.cuda.synchronize()
+    m["model_memory_allocated_with_cores_GB"] = round(mem_with / 1e9, 3)
+    m["model_memory_allocated_without_cores_GB"] = round((mem_with - (before - torch.cuda.memory_allocated())) / 1e9, 3)
+    m["prefill_buckets_without_cores_ms_per_prompt_token"] = prefill("buckets")
+    out["model"] = m
+    res["prefill_buckets"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r12_prefill_buckets.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def prefill_attention(b, res):
     """Prefill attention: effort_attention_rows (every query of a block reads K / V again) beside effort_attention_block (the block's
     queries share each K / V tile), one process.  Kernel legs, decode_prefill's protocol: 32 heads, headDim 128, maxTokens 8192, a pass
@@ -770,7 +898,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
-       "prefill_mixtral": prefill_mixtral}
+       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets}
 
 
 class Light:

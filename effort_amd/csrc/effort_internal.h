@@ -271,17 +271,6 @@ hipError_t launch_moe_route_rows(const float* h, const uint16_t* w, const uint16
                                  uint32_t* idx, float* val, uint32_t rows, hipStream_t st);
 hipError_t launch_mix2_add_rows(float* h, const float* f, const float* val, uint32_t n, uint32_t rows, hipStream_t st);
 
-// prompt prefill (prefill.hip): the block multiply
-bool dense_gemm_rows_supported(uint32_t inDim, uint32_t outDim);
-size_t dense_gemm_rows_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows);      // scratch for the k splits' partial sums (0: none)
-hipError_t launch_dense_gemm_rows(const uint16_t* W_f16, const float* x, uint16_t* xhScratch /* rows * inDim halves */, float* partScratch, float* out,
-                                  uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
-// ... and its routed form: assignment 2 r + s multiplies expert idx2[2 r + s] of a stack (numExperts <= 64)
-size_t dense_gemm_rows_routed_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows);
-size_t dense_gemm_rows_routed_group_words();                                              // scratch for the per-expert counts and assignment lists
-hipError_t launch_dense_gemm_rows_routed(const uint16_t* W_f16, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot,
-                                         uint16_t* xhScratch /* (xPerSlot ? 2 : 1) * rows * inDim halves */, float* partScratch, uint32_t* groupScratch,
-                                         float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
 // prefill attention with the block's queries sharing each K / V tile (attention_block.hip): flash-style, f32 MFMA, headDim 64 / 128 / 256
 hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
                                   uint32_t numHeads, uint32_t headDim, hipStream_t st);

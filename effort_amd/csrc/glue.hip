@@ -141,16 +141,27 @@ extern "C" int effort_fetch_row(effort_ctx* c, const void* emb, const uint32_t* 
 // the pointers, the lanes are joined before the launch.
 static_assert(EFFORT_PREFILL_MAX_ROWS == 64, "prefill.hip: kPrefillMaxRows, four token tiles of 16");
 static bool prefill_rows_ok(int rows) { return rows >= 1 && rows <= EFFORT_PREFILL_MAX_ROWS; }
+// The scratch of a block multiply, on cores or buckets (both are eager on the context's stream, neither outlives its launches' reads),
+// grown to a full block's worth whatever rows and xPerSlot are: the next, longer block and the w1, w3 and w2 calls of a layer do not
+// allocate again.  A routed call has its OWN set (host.h: captured addresses).
+static int grow_block_scratch(effort_ctx* c, uint32_t inDim, uint32_t outDim, int rows, bool routed, int xPerSlot = 0) {
+    if (!routed) {
+        OK_TRY(c->d_xhRows.grow(c, (size_t)rows * inDim, (size_t)EFFORT_PREFILL_MAX_ROWS * inDim));
+        return c->d_gemmPart.grow(c, dense_gemm_rows_partial_floats(inDim, outDim, (uint32_t)rows),
+                                  dense_gemm_rows_partial_floats(inDim, outDim, EFFORT_PREFILL_MAX_ROWS));
+    }
+    OK_TRY(c->d_xhRouted.grow(c, (size_t)(xPerSlot ? 2 : 1) * rows * inDim, (size_t)2 * EFFORT_PREFILL_MAX_ROWS * inDim));
+    OK_TRY(c->d_routedPart.grow(c, dense_gemm_rows_routed_partial_floats(inDim, outDim, (uint32_t)rows),
+                                dense_gemm_rows_routed_partial_floats(inDim, outDim, EFFORT_PREFILL_MAX_ROWS)));
+    return c->d_routedGroups.grow(c, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words());
+}
 extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float* x, float* out, int inDim, int outDim, int rows) {
     if (inDim <= 0 || outDim <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows: inDim, outDim >= 1, 1 <= rows <= 64");
     if (!dense_gemm_rows_supported((uint32_t)inDim, (uint32_t)outDim))
         return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, W below 4 GiB");
     if (!c || !W || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows: null argument");
     JOIN_TRY(c);
-    // (a block's worth of both: the next, longer block does not allocate again)
-    OK_TRY(c->d_xhRows.grow(c, (size_t)rows * inDim, (size_t)EFFORT_PREFILL_MAX_ROWS * inDim));
-    OK_TRY(c->d_gemmPart.grow(c, dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows),
-                              dense_gemm_rows_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS)));
+    OK_TRY(grow_block_scratch(c, (uint32_t)inDim, (uint32_t)outDim, rows, false));
     return HIP_RC(c, launch_dense_gemm_rows(static_cast<const uint16_t*>(W), x, c->d_xhRows.buf, c->d_gemmPart.buf, out, (uint32_t)inDim, (uint32_t)outDim,
                                       (uint32_t)rows, c->stream));
 }
@@ -162,12 +173,7 @@ extern "C" int effort_dense_gemm_rows_routed(effort_ctx* c, const void* W, int n
         return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows_routed: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, one expert below 4 GiB, numExperts <= 64");
     if (!c || !W || !idx2 || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows_routed: null argument");
     JOIN_TRY(c);
-    // (grown to a full block's worth whatever xPerSlot and rows are: the w1, w3 and w2 calls of a layer allocate once)
-    const size_t xRows = (size_t)(xPerSlot ? 2 : 1) * rows;
-    OK_TRY(c->d_xhRouted.grow(c, xRows * inDim, (size_t)2 * EFFORT_PREFILL_MAX_ROWS * inDim));
-    OK_TRY(c->d_routedPart.grow(c, dense_gemm_rows_routed_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows),
-                                dense_gemm_rows_routed_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_MAX_ROWS)));
-    OK_TRY(c->d_routedGroups.grow(c, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words()));
+    OK_TRY(grow_block_scratch(c, (uint32_t)inDim, (uint32_t)outDim, rows, true, xPerSlot));
     return HIP_RC(c, launch_dense_gemm_rows_routed(static_cast<const uint16_t*>(W), (uint32_t)numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted.buf,
                                              c->d_routedPart.buf, c->d_routedGroups.buf, out, (uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows, c->stream));
 }
@@ -218,10 +224,7 @@ extern "C" int effort_bucket_gemm_rows(effort_ctx* c, const effort_w* w, int exp
     if (!c || c != w->ctx || !x || !out) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows: null argument (or a handle of another context)");
     JOIN_TRY(c);
     OK_TRY(bucket_refuse_collisions(c, w, "bucket_gemm_rows"));
-    // effort_dense_gemm_rows's scratch, the same sizes: both calls are eager on the context's stream, neither outlives its launches' reads
-    OK_TRY(c->d_xhRows.grow(c, (size_t)rows * w->inDim, (size_t)EFFORT_PREFILL_MAX_ROWS * w->inDim));
-    OK_TRY(c->d_gemmPart.grow(c, dense_gemm_rows_partial_floats(w->inDim, w->outDim, (uint32_t)rows),
-                              dense_gemm_rows_partial_floats(w->inDim, w->outDim, EFFORT_PREFILL_MAX_ROWS)));
+    OK_TRY(grow_block_scratch(c, w->inDim, w->outDim, rows, false));
     const uint16_t* B = reinterpret_cast<const uint16_t*>(reinterpret_cast<const unsigned char*>(w->buckets) + (size_t)expert * 16u * w->inDim * w->rowPitch);
     return HIP_RC(c, launch_bucket_gemm_rows(B, w->rowPitch, x, c->d_xhRows.buf, c->d_gemmPart.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
 }
@@ -233,12 +236,7 @@ extern "C" int effort_bucket_gemm_rows_routed(effort_ctx* c, const effort_w* w, 
     if (!c || c != w->ctx || !idx2 || !x || !out) return fail(c, EFFORT_ERR_ARG, "bucket_gemm_rows_routed: null argument (or a handle of another context)");
     JOIN_TRY(c);
     OK_TRY(bucket_refuse_collisions(c, w, "bucket_gemm_rows_routed"));
-    // effort_dense_gemm_rows_routed's scratch, the same sizes
-    const size_t xRows = (size_t)(xPerSlot ? 2 : 1) * rows;
-    OK_TRY(c->d_xhRouted.grow(c, xRows * w->inDim, (size_t)2 * EFFORT_PREFILL_MAX_ROWS * w->inDim));
-    OK_TRY(c->d_routedPart.grow(c, dense_gemm_rows_routed_partial_floats(w->inDim, w->outDim, (uint32_t)rows),
-                                dense_gemm_rows_routed_partial_floats(w->inDim, w->outDim, EFFORT_PREFILL_MAX_ROWS)));
-    OK_TRY(c->d_routedGroups.grow(c, dense_gemm_rows_routed_group_words(), dense_gemm_rows_routed_group_words()));
+    OK_TRY(grow_block_scratch(c, w->inDim, w->outDim, rows, true, xPerSlot));
     return HIP_RC(c, launch_bucket_gemm_rows_routed(w->buckets, w->rowPitch, w->numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted.buf, c->d_routedPart.buf,
                                               c->d_routedGroups.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
 }

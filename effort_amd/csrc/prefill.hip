@@ -236,71 +236,13 @@ size_t dense_gemm_rows_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t 
     return sp.splits > 1u ? (size_t)sp.splits * rows * outDim : 0;
 }
 
-template <int NT, int AUX>
-static hipError_t launch_dense_gemm_rows_t(const uint16_t* W, const uint16_t* xh, float* dst, uint32_t inDim, uint32_t outDim, uint32_t rows,
-                                           PfSplit sp, hipStream_t st) {
-    hipLaunchKernelGGL((dense_gemm_rows_kernel<NT, AUX>), dim3((outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves), sp.splits), dim3(64 * kPfWaves), 0, st,
-                       W, xh, dst, inDim, outDim, rows, sp.per);
-    return hipGetLastError();
-}
-
-// xh: scratch of rows * inDim halves; part: scratch of dense_gemm_rows_partial_floats floats
-hipError_t launch_dense_gemm_rows(const uint16_t* W, const float* x, uint16_t* xh, float* part, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows,
-                                  hipStream_t st) {
-    if (rows < 1u || rows > (uint32_t)kPrefillMaxRows) return hipErrorInvalidValue;
-    const uint32_t n = rows * inDim;
-    hipLaunchKernelGGL(rows_to_f16_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, x, xh, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const PfSplit sp = pf_split(inDim, outDim);
-    float* dst = sp.splits > 1u ? part : out;
-    const bool nt = (size_t)inDim * outDim * 2u > kPfKeepBytes;
-    switch ((rows + 15u) / 16u) {
-        case 1: e = nt ? launch_dense_gemm_rows_t<1, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<1, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
-        case 2: e = nt ? launch_dense_gemm_rows_t<2, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<2, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
-        case 3: e = nt ? launch_dense_gemm_rows_t<3, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<3, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
-        default: e = nt ? launch_dense_gemm_rows_t<4, 2>(W, xh, dst, inDim, outDim, rows, sp, st) : launch_dense_gemm_rows_t<4, 0>(W, xh, dst, inDim, outDim, rows, sp, st); break;
-    }
-    if (e != hipSuccess || sp.splits == 1u) return e;
-    const uint32_t no = rows * outDim;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((no + 255u) / 256u), dim3(256), 0, st, part, out, no, sp.splits);
-    return hipGetLastError();
-}
-
 // floats of context scratch the partial sums of a routed call need: 2 * rows assignment rows per split
 size_t dense_gemm_rows_routed_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows) {
     return dense_gemm_rows_partial_floats(inDim, outDim, 2u * rows);
 }
 size_t dense_gemm_rows_routed_group_words() { return (size_t)kPfMaxExperts * (1u + kPfMaxAssign); }
 
-// xh: scratch of (xPerSlot ? 2 * rows : rows) * inDim halves; part: dense_gemm_rows_routed_partial_floats floats; groups:
-// dense_gemm_rows_routed_group_words words (the counts, then the lists).  out f32 [rows][2][outDim].
-hipError_t launch_dense_gemm_rows_routed(const uint16_t* W, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot, uint16_t* xh,
-                                         float* part, uint32_t* groups, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st) {
-    if (rows < 1u || rows > (uint32_t)kPrefillMaxRows || numExperts < 1u || numExperts > kPfMaxExperts || xPerSlot > 1u) return hipErrorInvalidValue;
-    const uint32_t assigns = 2u * rows, xRows = xPerSlot ? assigns : rows, n = xRows * inDim;
-    uint32_t* cnt = groups;
-    uint32_t* list = groups + kPfMaxExperts;
-    hipLaunchKernelGGL(routed_prologue_kernel, dim3((n + 255u) / 256u + 1u), dim3(256), 0, st, x, xh, n, idx2, assigns, numExperts, cnt, list);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const PfSplit sp = pf_split(inDim, outDim);
-    float* dst = sp.splits > 1u ? part : out;
-    const dim3 grid((outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves), sp.splits, numExperts);
-    if ((size_t)inDim * outDim * 2u > kPfKeepBytes)                               // by ONE expert's matrix: what a workgroup's neighbours stream with it
-        hipLaunchKernelGGL((dense_gemm_rows_routed_kernel<2>), grid, dim3(64 * kPfWaves), 0, st, W, xh, dst, cnt, list, inDim, outDim, assigns, xRows,
-                           xPerSlot ? 0u : 1u, sp.per);
-    else
-        hipLaunchKernelGGL((dense_gemm_rows_routed_kernel<0>), grid, dim3(64 * kPfWaves), 0, st, W, xh, dst, cnt, list, inDim, outDim, assigns, xRows,
-                           xPerSlot ? 0u : 1u, sp.per);
-    e = hipGetLastError();
-    if (e != hipSuccess || sp.splits == 1u) return e;
-    const uint32_t no = assigns * outDim;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((no + 255u) / 256u), dim3(256), 0, st, part, out, no, sp.splits);
-    return hipGetLastError();
-}
-
-// ---- the launches prefill_buckets.hip shares (prefill.h)
+// ---- the launches around the multiply (prefill.h), shared with prefill_buckets.hip
 hipError_t launch_rows_to_f16(const float* x, uint16_t* xh, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(rows_to_f16_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, x, xh, n);
     return hipGetLastError();
@@ -313,6 +255,29 @@ hipError_t launch_routed_prologue(const float* x, uint16_t* xh, uint32_t n, cons
                                   uint32_t* list, hipStream_t st) {
     hipLaunchKernelGGL(routed_prologue_kernel, dim3((n + 255u) / 256u + 1u), dim3(256), 0, st, x, xh, n, idx2, assigns, numExperts, cnt, list);
     return hipGetLastError();
+}
+
+// ---- the two launchers: pf_block_call (prefill.h) around the core kernels
+// xh: scratch of rows * inDim halves; part: scratch of dense_gemm_rows_partial_floats floats
+hipError_t launch_dense_gemm_rows(const uint16_t* W, const float* x, uint16_t* xh, float* part, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows,
+                                  hipStream_t st) {
+    return pf_block_call(PfCall{x, xh, part, out, inDim, outDim, rows}, st, [&](auto aux, const PfMul& m) {
+        return pf_with_tiles(rows, [&](auto nt) {
+            hipLaunchKernelGGL((dense_gemm_rows_kernel<decltype(nt)::value, decltype(aux)::value>), dim3((outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves), m.sp.splits),
+                               dim3(64 * kPfWaves), 0, st, W, xh, m.dst, inDim, outDim, rows, m.sp.per);
+            return hipGetLastError();
+        });
+    });
+}
+// xh: scratch of (xPerSlot ? 2 * rows : rows) * inDim halves; part: dense_gemm_rows_routed_partial_floats floats; groups:
+// dense_gemm_rows_routed_group_words words (the counts, then the lists).  out f32 [rows][2][outDim].
+hipError_t launch_dense_gemm_rows_routed(const uint16_t* W, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot, uint16_t* xh,
+                                         float* part, uint32_t* groups, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st) {
+    return pf_block_call(PfCall{x, xh, part, out, inDim, outDim, rows, true, idx2, groups, numExperts, xPerSlot}, st, [&](auto aux, const PfMul& m) {
+        hipLaunchKernelGGL((dense_gemm_rows_routed_kernel<decltype(aux)::value>), dim3((outDim + 16u * kPfWaves - 1u) / (16u * kPfWaves), m.sp.splits, numExperts),
+                           dim3(64 * kPfWaves), 0, st, W, xh, m.dst, m.cnt, m.list, inDim, outDim, m.assigns, m.xRows, m.xShift, m.sp.per);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace effort

@@ -29,8 +29,6 @@
 // of a row outside its 2 * columns payload is read, whatever the padding holds.
 // 32 columns is the narrowest piece that still reads half a 128-byte line of every row; it gives outDim / 512 workgroups per split
 // (8 x 4 splits for 4096 x 4096), which is why this kernel does not load the chip the way the core kernel's 64-row groups do.
-#include <type_traits>
-
 #include "prefill.h"
 
 namespace effort {
@@ -250,81 +248,46 @@ hipError_t launch_bucket_dense_check(const uint16_t* B, uint32_t pitch, uint32_t
     return hipGetLastError();
 }
 
+// 16-byte row pieces (VEC 4) where every piece is one, 4-byte pieces (VEC 1) otherwise.  (Every expert's base is a multiple of
+// 16 * inDim * pitch bytes behind B: 16-byte aligned with B when the pitch is.)
 static bool bucket_wide(const uint16_t* B, uint32_t pitch, uint32_t cols) {
     return pitch % 16u == 0 && reinterpret_cast<uintptr_t>(B) % 16u == 0 && cols % 8u == 0;
 }
 
-template <int NT, int AUX, int VEC>
-static hipError_t launch_bucket_gemm_rows_t(const uint16_t* B, uint32_t pitch, uint32_t cols, const uint16_t* xh, float* dst, uint32_t inDim,
-                                            uint32_t outDim, uint32_t rows, PfSplit sp, hipStream_t st) {
-    const hipError_t e = allow_full_lds(reinterpret_cast<const void*>(&bucket_gemm_rows_kernel<NT, AUX, VEC>));
+// ---- the two launchers: pf_block_call (prefill.h) around the bucket kernels
+// kernel<...> on `grid` with the bucket kernels' block and all of the LDS
+template <class K, class... Args>
+static hipError_t launch_bk(K kernel, dim3 grid, hipStream_t st, Args... args) {
+    const hipError_t e = allow_full_lds(reinterpret_cast<const void*>(kernel));
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((bucket_gemm_rows_kernel<NT, AUX, VEC>), dim3((cols + kBkCols - 1u) / kBkCols, sp.splits), dim3(kBkThreads), kBkLds, st,
-                       B, pitch, cols, xh, dst, inDim, outDim, rows, sp.per);
+    hipLaunchKernelGGL(kernel, grid, dim3(kBkThreads), kBkLds, st, args...);
     return hipGetLastError();
-}
-template <int NT>
-static hipError_t launch_bucket_gemm_rows_nt(bool nt, bool wide, const uint16_t* B, uint32_t pitch, uint32_t cols, const uint16_t* xh, float* dst,
-                                             uint32_t inDim, uint32_t outDim, uint32_t rows, PfSplit sp, hipStream_t st) {
-    if (nt) return wide ? launch_bucket_gemm_rows_t<NT, 2, 4>(B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st)
-                        : launch_bucket_gemm_rows_t<NT, 2, 1>(B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st);
-    return wide ? launch_bucket_gemm_rows_t<NT, 0, 4>(B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st)
-                : launch_bucket_gemm_rows_t<NT, 0, 1>(B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st);
 }
 
 // B: ONE expert's buckets (percentLoad 16), bucket rows `pitch` bytes apart; xh, part: launch_dense_gemm_rows's scratch, the same sizes
 hipError_t launch_bucket_gemm_rows(const uint16_t* B, uint32_t pitch, const float* x, uint16_t* xh, float* part, float* out, uint32_t inDim,
                                    uint32_t outDim, uint32_t rows, hipStream_t st) {
-    if (rows < 1u || rows > (uint32_t)kPrefillMaxRows) return hipErrorInvalidValue;
-    hipError_t e = launch_rows_to_f16(x, xh, rows * inDim, st);
-    if (e != hipSuccess) return e;
-    const PfSplit sp = pf_split(inDim, outDim);
-    float* dst = sp.splits > 1u ? part : out;
     const uint32_t cols = outDim / 16u;
-    const bool nt = (size_t)inDim * outDim * 2u > kPfKeepBytes, wide = bucket_wide(B, pitch, cols);
-    switch ((rows + 15u) / 16u) {
-        case 1: e = launch_bucket_gemm_rows_nt<1>(nt, wide, B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st); break;
-        case 2: e = launch_bucket_gemm_rows_nt<2>(nt, wide, B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st); break;
-        case 3: e = launch_bucket_gemm_rows_nt<3>(nt, wide, B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st); break;
-        default: e = launch_bucket_gemm_rows_nt<4>(nt, wide, B, pitch, cols, xh, dst, inDim, outDim, rows, sp, st); break;
-    }
-    if (e != hipSuccess || sp.splits == 1u) return e;
-    return launch_reduce_splits(part, out, rows * outDim, sp.splits, st);
+    return pf_block_call(PfCall{x, xh, part, out, inDim, outDim, rows}, st, [&](auto aux, const PfMul& m) {
+        return pf_with_either<1, 4>(bucket_wide(B, pitch, cols), [&](auto vec) {
+            return pf_with_tiles(rows, [&](auto nt) {
+                return launch_bk(&bucket_gemm_rows_kernel<decltype(nt)::value, decltype(aux)::value, decltype(vec)::value>,
+                                 dim3((cols + kBkCols - 1u) / kBkCols, m.sp.splits), st, B, pitch, cols, xh, m.dst, inDim, outDim, rows, m.sp.per);
+            });
+        });
+    });
 }
-
-template <int AUX, int VEC>
-static hipError_t launch_bucket_gemm_rows_routed_t(const uint16_t* B, uint32_t pitch, uint32_t cols, uint32_t numExperts, const uint16_t* xh, float* dst,
-                                                   const uint32_t* cnt, const uint32_t* list, uint32_t inDim, uint32_t outDim, uint32_t assigns,
-                                                   uint32_t xRows, uint32_t xShift, PfSplit sp, hipStream_t st) {
-    const hipError_t e = allow_full_lds(reinterpret_cast<const void*>(&bucket_gemm_rows_routed_kernel<AUX, VEC>));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((bucket_gemm_rows_routed_kernel<AUX, VEC>), dim3((cols + kBkCols - 1u) / kBkCols, sp.splits, numExperts), dim3(kBkThreads), kBkLds, st,
-                       B, pitch, cols, xh, dst, cnt, list, inDim, outDim, assigns, xRows, xShift, sp.per);
-    return hipGetLastError();
-}
-
 // B: the whole stack's buckets; xh, part, groups: launch_dense_gemm_rows_routed's scratch, the same sizes.  out f32 [rows][2][outDim].
 hipError_t launch_bucket_gemm_rows_routed(const uint16_t* B, uint32_t pitch, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot,
                                           uint16_t* xh, float* part, uint32_t* groups, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows,
                                           hipStream_t st) {
-    if (rows < 1u || rows > (uint32_t)kPrefillMaxRows || numExperts < 1u || numExperts > kPfMaxExperts || xPerSlot > 1u) return hipErrorInvalidValue;
-    const uint32_t assigns = 2u * rows, xRows = xPerSlot ? assigns : rows, cols = outDim / 16u;
-    uint32_t* cnt = groups;
-    uint32_t* list = groups + kPfMaxExperts;
-    hipError_t e = launch_routed_prologue(x, xh, xRows * inDim, idx2, assigns, numExperts, cnt, list, st);
-    if (e != hipSuccess) return e;
-    const PfSplit sp = pf_split(inDim, outDim);
-    float* dst = sp.splits > 1u ? part : out;
-    const uint32_t xShift = xPerSlot ? 0u : 1u;
-    const bool nt = (size_t)inDim * outDim * 2u > kPfKeepBytes;                         // by ONE expert's matrix, as the core kernel decides
-    // (every expert's base is a multiple of 16 * inDim * pitch bytes behind B: 16-byte aligned with B when the pitch is)
-    const bool wide = bucket_wide(B, pitch, cols);
-    if (nt) e = wide ? launch_bucket_gemm_rows_routed_t<2, 4>(B, pitch, cols, numExperts, xh, dst, cnt, list, inDim, outDim, assigns, xRows, xShift, sp, st)
-                     : launch_bucket_gemm_rows_routed_t<2, 1>(B, pitch, cols, numExperts, xh, dst, cnt, list, inDim, outDim, assigns, xRows, xShift, sp, st);
-    else e = wide ? launch_bucket_gemm_rows_routed_t<0, 4>(B, pitch, cols, numExperts, xh, dst, cnt, list, inDim, outDim, assigns, xRows, xShift, sp, st)
-                  : launch_bucket_gemm_rows_routed_t<0, 1>(B, pitch, cols, numExperts, xh, dst, cnt, list, inDim, outDim, assigns, xRows, xShift, sp, st);
-    if (e != hipSuccess || sp.splits == 1u) return e;
-    return launch_reduce_splits(part, out, assigns * outDim, sp.splits, st);
+    const uint32_t cols = outDim / 16u;
+    return pf_block_call(PfCall{x, xh, part, out, inDim, outDim, rows, true, idx2, groups, numExperts, xPerSlot}, st, [&](auto aux, const PfMul& m) {
+        return pf_with_either<1, 4>(bucket_wide(B, pitch, cols), [&](auto vec) {
+            return launch_bk(&bucket_gemm_rows_routed_kernel<decltype(aux)::value, decltype(vec)::value>, dim3((cols + kBkCols - 1u) / kBkCols, m.sp.splits, numExperts),
+                             st, B, pitch, cols, xh, m.dst, m.cnt, m.list, inDim, outDim, m.assigns, m.xRows, m.xShift, m.sp.per);
+        });
+    });
 }
 
 }  // namespace effort

@@ -485,42 +485,47 @@ class Decoder:
             self.pf_gateOut = torch.zeros((cfg.numLayers, chunk, cfg.numExperts), dtype=torch.float32, device=dev)
         self._pf = chunk
 
-    def _gemm_rows(self, x, core, out, rows: int):
-        """out[r] = core * f16(x[r]) for the first ``rows`` rows: ONE pass over the matrix (effort_dense_gemm_rows).  A matrix the block
-        kernel refuses (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMul`` row by row, as ``_dense_experts`` falls back."""
-        g = self.g
-        rc = _lib.lib().effort_dense_gemm_rows(g.ctx, _p(core), _p(x), _p(out), int(core.shape[1]), int(core.shape[0]), rows)
-        if rc == -2:
-            for r in range(rows):
-                basicMul(x[r], core, out[r])
-            return
-        g.check(rc, "dense_gemm_rows")
+    def _block_multiplies(self, from_buckets: bool):
+        """The two block multiplies of a ``prefill`` walk, chosen once per call by ``weights``:
 
-    def _gemm_rows_routed(self, x, cores, idx2, out, rows: int, per_slot: bool):
-        """out[r][s] = cores[idx2[r][s]] * f16(x[r]) -- ``per_slot``: * f16(x[r][s]) -- for the first ``rows`` tokens: every picked expert's
-        matrix is read ONCE for all the tokens that picked it (effort_dense_gemm_rows_routed).  A stack the kernel refuses
-        (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMulExpert`` per assignment, as ``_gemm_rows`` falls back."""
-        g = self.g
-        E, o, i = (int(d) for d in cores.shape)
-        rc = _lib.lib().effort_dense_gemm_rows_routed(g.ctx, _p(cores), E, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), i, o, rows)
-        if rc == -2:
-            for r in range(rows):
-                for sl in range(2):
-                    basicMulExpert(x[r][sl] if per_slot else x[r], cores, idx2[r][sl:sl + 1], out[r][sl])
-            return
-        g.check(rc, "dense_gemm_rows_routed")
+        ``mul(x, ew, out, rows)``: out[r] = M * f16(x[r]) for the first ``rows`` rows, ONE pass over the matrix;
+        ``mul_routed(x, ew, idx2, out, rows, per_slot)``: out[r][s] = M[idx2[r][s]] * f16(x[r]) -- ``per_slot``: * f16(x[r][s]) --, every
+        picked expert's matrix read ONCE for all the tokens that picked it.
 
-    def _bucket_rows(self, x, ew, out, rows: int):
-        """out[r] = U * f16(x[r]) for the first ``rows`` rows, U the un-bucketed matrix of ``ew`` (effort_bucket_gemm_rows): no core is
-        read.  No fallback: every refusal of the library was ruled out by ``prefill`` before anything was enqueued, so one is an error."""
-        g = self.g
-        g.check(_lib.lib().effort_bucket_gemm_rows(g.ctx, ew.handle, 0, _p(x), _p(out), rows), "bucket_gemm_rows")
+        On the cores M is ``ew.core`` (effort_dense_gemm_rows / effort_dense_gemm_rows_routed); a matrix the block kernel refuses
+        (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMul`` row by row, a stack to ``basicMulExpert`` per assignment, as
+        ``_dense_experts`` falls back.  On the buckets M is the un-bucketed matrix of ``ew`` (effort_bucket_gemm_rows /
+        effort_bucket_gemm_rows_routed): no core is read, and there is no fallback -- every refusal of the library was ruled out by
+        ``prefill`` before anything was enqueued, so one is an error."""
+        g, lib = self.g, _lib.lib()
+        if from_buckets:
+            def mul(x, ew, out, rows):
+                g.check(lib.effort_bucket_gemm_rows(g.ctx, ew.handle, 0, _p(x), _p(out), rows), "bucket_gemm_rows")
 
-    def _bucket_rows_routed(self, x, ew, idx2, out, rows: int, per_slot: bool):
-        """``_gemm_rows_routed`` on the un-bucketed expert stack of ``ew`` (effort_bucket_gemm_rows_routed); no fallback either."""
-        g = self.g
-        g.check(_lib.lib().effort_bucket_gemm_rows_routed(g.ctx, ew.handle, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), rows),
-                "bucket_gemm_rows_routed")
+            def mul_routed(x, ew, idx2, out, rows, per_slot):
+                g.check(lib.effort_bucket_gemm_rows_routed(g.ctx, ew.handle, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), rows), "bucket_gemm_rows_routed")
+            return mul, mul_routed
+
+        def mul(x, ew, out, rows):
+            core = ew.core
+            rc = lib.effort_dense_gemm_rows(g.ctx, _p(core), _p(x), _p(out), int(core.shape[1]), int(core.shape[0]), rows)
+            if rc == -2:
+                for r in range(rows):
+                    basicMul(x[r], core, out[r])
+                return
+            g.check(rc, "dense_gemm_rows")
+
+        def mul_routed(x, ew, idx2, out, rows, per_slot):
+            cores = ew.core
+            E, o, i = (int(d) for d in cores.shape)
+            rc = lib.effort_dense_gemm_rows_routed(g.ctx, _p(cores), E, _p(idx2), _p(x), 1 if per_slot else 0, _p(out), i, o, rows)
+            if rc == -2:
+                for r in range(rows):
+                    for sl in range(2):
+                        basicMulExpert(x[r][sl] if per_slot else x[r], cores, idx2[r][sl:sl + 1], out[r][sl])
+                return
+            g.check(rc, "dense_gemm_rows_routed")
+        return mul, mul_routed
 
     def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense",
                 weights: str = "cores"):
@@ -608,12 +613,7 @@ class Decoder:
         self._prefill_buffers(chunk)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
         rope = C.c_float(cfg.ropeBase)
-        if from_buckets:
-            mul = lambda x, ew, out, rows: self._bucket_rows(x, ew, out, rows)                             # noqa: E731
-            mul_routed = lambda x, ew, idx2, out, rows, per_slot: self._bucket_rows_routed(x, ew, idx2, out, rows, per_slot)   # noqa: E731
-        else:
-            mul = lambda x, ew, out, rows: self._gemm_rows(x, ew.core, out, rows)                          # noqa: E731
-            mul_routed = lambda x, ew, idx2, out, rows, per_slot: self._gemm_rows_routed(x, ew.core, idx2, out, rows, per_slot)   # noqa: E731
+        mul, mul_routed = self._block_multiplies(from_buckets)
         for b0 in range(0, T, chunk):
             rows, p = min(chunk, T - b0), pos0 + b0
             self.pf_ids[:rows].copy_(torch.tensor(ids[b0:b0 + rows], dtype=torch.int32))

@@ -286,46 +286,61 @@ def test_refusals_enqueue_nothing(gpu):
 
 
 # ---------------------------------------------------------------- 5. the routed front end
-EXPERTS = 4
 _STACKS = {}
 
 
-def stack_of(outDim):
-    """(clean bundle, per-(expert, input row id) cache of the plain call's row), one per outDim; never rewritten."""
-    if outDim not in _STACKS:
-        _STACKS[outDim] = (Bundle(outDim, 4096, E=EXPERTS, pitch=(outDim // 16 * 2 + 127) // 128 * 128, seed=9), {})
-    return _STACKS[outDim]
+def stack_of(outDim, inDim, pitch, E):
+    """(clean bundle, per-(expert, input row id) cache of the plain call's row), one per (shape, pitch, expert count); never rewritten."""
+    key = (outDim, inDim, pitch, E)
+    if key not in _STACKS:
+        _STACKS[key] = (Bundle(outDim, inDim, E=E, pitch=pitch, seed=9), {})
+    return _STACKS[key]
 
 
-def routing(kind, rows, seed):
+def routing(kind, rows, seed, E):
     rng = np.random.default_rng(seed)
     if kind == "random":                                     # two distinct experts per token
-        idx = np.stack([rng.permutation(EXPERTS)[:2] for _ in range(rows)])
+        idx = np.stack([rng.permutation(E)[:2] for _ in range(rows)])
     elif kind == "one":                                      # every assignment on expert 2: up to 128 columns, walked 64 at a time
         idx = np.full((rows, 2), 2)
     else:                                                    # "clamped": out-of-range expert numbers mean the last expert
-        idx = np.stack([rng.permutation(EXPERTS)[:2] for _ in range(rows)])
+        idx = np.stack([rng.permutation(E)[:2] for _ in range(rows)])
         idx[::2, 1] = 7
         idx[-1, 0] = 0xFFFFFFFF
     return idx.astype(np.uint32)
 
 
-@pytest.mark.parametrize("xPerSlot", (0, 1))
-@pytest.mark.parametrize("kind", ("random", "one", "clamped"))
-@pytest.mark.parametrize("rows", (1, 17, 64))
-@pytest.mark.parametrize("outDim", (64, 1056))
-def test_routed_is_the_plain_call_per_assignment(gpu, outDim, rows, kind, xPerSlot):
-    clean, cache = stack_of(outDim)
-    idx = routing(kind, rows, seed=outDim + rows)
-    picked = np.minimum(idx.reshape(-1), EXPERTS - 1)
+# (outDim, inDim, pitch in bytes or None, experts, rows, kind, xPerSlot) and the instantiation <AUX 0 | 2 (nt), VEC 4 | 1 (dwords per
+# load)> of the routed kernel each reaches.  nt is judged by ONE expert's matrix (above 64 MiB), so the two large stacks cannot be smaller;
+# two experts is the fewest that still routes.
+def _routed(outDim, inDim, pitch, E, rows, kind, xPerSlot):
+    return pytest.param(outDim, inDim, pitch, E, rows, kind, xPerSlot, id=f"{outDim}-{rows}-{kind}-{xPerSlot}")
+
+
+ROUTED_CASES = [
+    # 4 and 66 columns on whole lines (pitch 128, 256): no multiple of 8 columns, 4-byte pieces: <0, 1>
+    *[_routed(outDim, 4096, (outDim // 16 * 2 + 127) // 128 * 128, 4, rows, kind, xPerSlot)
+      for xPerSlot in (0, 1) for kind in ("random", "one", "clamped") for rows in (1, 17, 64) for outDim in (64, 1056)],
+    # 8 columns, 16-byte pieces: <0, 4>
+    *[_routed(128, 4096, 128, 4, 17, kind, xPerSlot) for xPerSlot in (0, 1) for kind in ("random", "one")],
+    _routed(8192, 4224, 1024, 2, 16, "random", 0),           # one expert above 64 MiB, 16-byte pieces: <2, 4>
+    _routed(8224, 4096, None, 2, 16, "random", 0),           # above 64 MiB, 514 columns on the dense pitch of 1028: 4-byte pieces: <2, 1>
+]
+
+
+@pytest.mark.parametrize("outDim,inDim,pitch,E,rows,kind,xPerSlot", ROUTED_CASES)
+def test_routed_is_the_plain_call_per_assignment(gpu, outDim, inDim, pitch, E, rows, kind, xPerSlot):
+    clean, cache = stack_of(outDim, inDim, pitch, E)
+    idx = routing(kind, rows, seed=outDim + rows, E=E)
+    picked = np.minimum(idx.reshape(-1), E - 1)
     b = clean
-    unpicked = sorted(set(range(EXPERTS)) - set(picked.tolist()))
+    unpicked = sorted(set(range(E)) - set(picked.tolist()))
     if unpicked:                                             # a never-picked expert's buckets are NaN: a copy of the stack, poisoned
-        b = Bundle(outDim, 4096, E=EXPERTS, pitch=clean.ew.rowPitch, seed=9)
+        b = Bundle(outDim, inDim, E=E, pitch=pitch, seed=9)
         assert torch.equal(b.words, clean.words)
         b.poison(unpicked)
         b.ew.refresh()
-    xsrc = x_rows(4096)
+    xsrc = x_rows(inDim)
     xRows = (2 if xPerSlot else 1) * rows
     x = padded_x(xsrc, xRows, alloc=2 * MAX_ROWS)
     idx_d = torch.full((2 * MAX_ROWS,), 3, dtype=torch.int32, device=DEV)

@@ -408,6 +408,59 @@ def decode_sampled(b, res):
     del dec, model
 
 
+# ---- what the four prefill sections measure with
+def us_per_call(b, fn, calls):
+    """us per library call of ``fn`` (``calls`` of them, enqueued on the context's stream): one warm call (the first bucket call of a
+    handle runs its check, which synchronises), ``fn`` captured into one graph, 3 warm replays, then device events around 4 replays per
+    window, best of 3 windows."""
+    torch, g = b.torch, b.g
+    g._bind_stream()
+    fn()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    B._GRAPHS_FOR_LIFE.append(gr)
+    with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+        fn()
+    g._bind_stream()
+    for _ in range(3):
+        gr.replay()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(4):
+            gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
+    return best
+
+
+def timed_prefill(b, dec, prompt, **kw):
+    """ms per prompt token of ``dec.prefill(prompt, **kw)``: eager, synchronised wall time over the whole prompt, best of 3 after a warm
+    call (it makes the buffers, warms the kernels and runs every handle's check; not timed)."""
+    torch = b.torch
+    dec.prefill(prompt, **kw)
+    best = float("inf")
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec.prefill(prompt, **kw)
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return round(best * 1e3 / len(prompt), 4)
+
+
+def token_loop(dec, prompt, **kw):
+    """ms per prompt token of the prompt ingested token by token through the captured step, best of 2 runs."""
+    best = float("inf")
+    for _ in range(2):
+        _, dt, _ = dec.run(prompt, len(prompt), **kw)
+        best = min(best, dt)
+    return round(best * 1e3, 4)
+
+
 def decode_prefill(b, res):
     """Prompt ingest.  Kernel legs: effort_dense_gemm_rows at rows = 1, 16, 64 beside effort_dense_gemv on the decode loop's four matrix
     shapes -- a pass over ROTATING disjoint matrices (more than 768 MB of them per shape: nothing of a matrix is still cached when its
@@ -427,29 +480,6 @@ def decode_prefill(b, res):
     p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
     gen = torch.Generator(device=b.dev)
     gen.manual_seed(77)
-
-    def us_per_call(fn, calls):
-        g._bind_stream()
-        fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        B._GRAPHS_FOR_LIFE.append(gr)
-        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-            fn()
-        g._bind_stream()
-        for _ in range(3):
-            gr.replay()
-        torch.cuda.synchronize()
-        best = float("inf")
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(4):
-                gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
-        return best
 
     kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events; TB/s = weight bytes / time"}
     for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
@@ -472,7 +502,7 @@ def decode_prefill(b, res):
             return fn
         row = {"matrices": count, "weight_bytes": nbytes}
         for name, fn in (("dense_gemv", gemv), ("gemm_rows_1", gemm(1)), ("gemm_rows_16", gemm(16)), ("gemm_rows_64", gemm(64))):
-            us = us_per_call(fn, count)
+            us = us_per_call(b, fn, count)
             row[name] = {"us_per_call": round(us, 2), "TBps_of_weight_bytes": round(nbytes / us / 1e6, 3)}
         for rows in (1, 16, 64):
             row[f"gemm_rows_{rows}_over_gemv_time"] = round(row[f"gemm_rows_{rows}"]["us_per_call"] / row["dense_gemv"]["us_per_call"], 3)
@@ -487,32 +517,15 @@ def decode_prefill(b, res):
     B._GRAPHS_FOR_LIFE.append(dec._graphs)
     prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
 
-    def token_loop(**kw):
-        best = float("inf")
-        for _ in range(2):
-            _, dt, _ = dec.run(prompt, nprompt, **kw)
-            best = min(best, dt)
-        return round(best * 1e3, 4)
-
-    def prefill(chunk):
-        dec.prefill(prompt, chunk=chunk)                         # the warm call: it makes the buffers and warms the kernels; not timed
-        best = float("inf")
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            dec.prefill(prompt, chunk=chunk)
-            torch.cuda.synchronize()
-            best = min(best, time.perf_counter() - t0)
-        return round(best * 1e3 / nprompt, 4)
     m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "prompt_tokens": nprompt,
          "protocol": "token loop: hipGraph replay of the step, timed from the 3rd step, best of 2 runs (LM head and pick in it); prefill: eager, "
                      "synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call (no LM head, the last layer "
                      "stops after its cache write)"}
-    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dense=True)
-    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(effort=0.25)
-    m["prefill_chunk_16_ms_per_prompt_token"] = prefill(16)
-    m["prefill_chunk_64_ms_per_prompt_token"] = prefill(64)
-    m["prefill_chunk_16_again_ms_per_prompt_token"] = prefill(16)
+    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dec, prompt, dense=True)
+    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(dec, prompt, effort=0.25)
+    m["prefill_chunk_16_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, chunk=16)
+    m["prefill_chunk_64_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, chunk=64)
+    m["prefill_chunk_16_again_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, chunk=16)
     ids, _, _ = dec.run(prompt, nprompt + 4, effort=0.25, prefill=True)
     m["run_prefill_true_last_prefill_s"] = round(dec.last_prefill_s, 5)
     m["run_prefill_true_picks"] = ids[nprompt - 1:]
@@ -551,29 +564,6 @@ def prefill_mixtral(b, res):
     gen.manual_seed(78)
     E = 8
 
-    def us_per_call(fn, calls):
-        g._bind_stream()
-        fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        B._GRAPHS_FOR_LIFE.append(gr)
-        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-            fn()
-        g._bind_stream()
-        for _ in range(3):
-            gr.replay()
-        torch.cuda.synchronize()
-        best = float("inf")
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(4):
-                gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
-        return best
-
     kern = {"protocol": "one pass over two rotating stacks per graph, 4 replays per window, best of 3 windows, device events; routing: two "
                         "different experts per token, uniform; dense_x8 = 8 x the time of one effort_dense_gemm_rows call on an expert's matrix"}
     for outD, inD in ((14336, 4096), (4096, 14336)):
@@ -595,7 +585,7 @@ def prefill_mixtral(b, res):
                     for e in range(E):
                         g.check(lib.effort_dense_gemm_rows(g.ctx, p(W[e]), p(x), p(out), inD, outD, rows), "dense_gemm_rows")
             picked = len(set(idx2[:rows].reshape(-1).tolist()))
-            r_us, d_us = us_per_call(routed, 2), 8 * us_per_call(dense, 2 * E)
+            r_us, d_us = us_per_call(b, routed, 2), 8 * us_per_call(b, dense, 2 * E)
             row[f"rows_{rows}"] = {"experts_picked": picked, "routed_us_per_call": round(r_us, 2), "dense_x8_us": round(d_us, 2),
                                    "routed_over_dense_x8": round(r_us / d_us, 3),
                                    "routed_TBps_of_picked_bytes": round(picked * outD * inD * 2 / r_us / 1e6, 3)}
@@ -610,33 +600,16 @@ def prefill_mixtral(b, res):
     B._GRAPHS_FOR_LIFE.append(dec._graphs)
     prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
 
-    def token_loop(**kw):
-        best = float("inf")
-        for _ in range(2):
-            _, dt, _ = dec.run(prompt, nprompt, **kw)
-            best = min(best, dt)
-        return round(best * 1e3, 4)
-
-    def prefill(chunk):
-        dec.prefill(prompt, chunk=chunk, ffn="routed")            # the warm call: it makes the buffers and warms the kernels; not timed
-        best = float("inf")
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            dec.prefill(prompt, chunk=chunk, ffn="routed")
-            torch.cuda.synchronize()
-            best = min(best, time.perf_counter() - t0)
-        return round(best * 1e3 / nprompt, 4)
     m = {"model": "Mixtral-8x7B shapes (4096 / 14336, 8 experts, top-2, 32 / 8 heads), 8 layers, STRUCTURED random weights, seed 1",
          "prompt_tokens": nprompt,
          "protocol": "token loop: hipGraph replay of the step, timed from the 3rd step, best of 2 runs (LM head and pick in it); prefill: eager, "
                      "synchronised wall time of Decoder.prefill(ffn='routed') over the whole prompt, best of 3 after a warm call (no LM head, the "
                      "last layer stops after its cache write)"}
-    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dense=True)
-    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(effort=0.25)
-    m["prefill_routed_chunk_16_ms_per_prompt_token"] = prefill(16)
-    m["prefill_routed_chunk_64_ms_per_prompt_token"] = prefill(64)
-    m["token_by_token_dense_again_ms_per_prompt_token"] = token_loop(dense=True)
+    m["token_by_token_dense_ms_per_prompt_token"] = token_loop(dec, prompt, dense=True)
+    m["token_by_token_effort_0.25_ms_per_prompt_token"] = token_loop(dec, prompt, effort=0.25)
+    m["prefill_routed_chunk_16_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, chunk=16, ffn="routed")
+    m["prefill_routed_chunk_64_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, chunk=64, ffn="routed")
+    m["token_by_token_dense_again_ms_per_prompt_token"] = token_loop(dec, prompt, dense=True)
     base, again = m["token_by_token_dense_ms_per_prompt_token"], m["token_by_token_dense_again_ms_per_prompt_token"]
     m["token_loop_legs_spread"] = round(abs(base - again) / min(base, again), 4)
     for k in ("token_by_token_effort_0.25", "prefill_routed_chunk_16", "prefill_routed_chunk_64"):
@@ -674,29 +647,6 @@ def prefill_buckets(b, res):
     gen = torch.Generator(device=b.dev)
     gen.manual_seed(78)
 
-    def us_per_call(fn, calls):
-        g._bind_stream()
-        fn()                                                                     # (warm: the first bucket call of a handle runs its check, which synchronises)
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        B._GRAPHS_FOR_LIFE.append(gr)
-        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-            fn()
-        g._bind_stream()
-        for _ in range(3):
-            gr.replay()
-        torch.cuda.synchronize()
-        best = float("inf")
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(4):
-                gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
-        return best
-
     kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events; both kernels in this run; "
                         "a workgroup of the bucket kernel owns 32 bucket columns (64 bytes of every bucket row, 512 outputs)"}
     for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
@@ -726,7 +676,7 @@ def prefill_buckets(b, res):
         row = {"matrices": count, "weight_bytes": nbytes, "bucket_row_pitch": ews[0].rowPitch}
         for rows in (16, 64):
             for name, fn in ((f"core_rows_{rows}", cores(rows)), (f"bucket_rows_{rows}", buckets(rows))):
-                us = us_per_call(fn, count)
+                us = us_per_call(b, fn, count)
                 row[name] = {"us_per_call": round(us, 2), "TBps_of_weight_bytes": round(nbytes / us / 1e6, 3)}
             row[f"bucket_over_core_time_{rows}"] = round(row[f"bucket_rows_{rows}"]["us_per_call"] / row[f"core_rows_{rows}"]["us_per_call"], 3)
         kern[f"{inD}->{outD}"] = row
@@ -742,21 +692,11 @@ def prefill_buckets(b, res):
     dec = Decoder(model, maxTokens=nprompt + 8)
     prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
 
-    def prefill(weights):
-        dec.prefill(prompt, weights=weights)                     # the warm call (and every handle's check); not timed
-        best = float("inf")
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            dec.prefill(prompt, weights=weights)
-            torch.cuda.synchronize()
-            best = min(best, time.perf_counter() - t0)
-        return round(best * 1e3 / nprompt, 4)
     m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "prompt_tokens": nprompt,
          "protocol": "eager, synchronised wall time of Decoder.prefill(chunk=64) over the whole prompt, best of 3 after a warm call"}
-    m["prefill_cores_ms_per_prompt_token"] = prefill("cores")
+    m["prefill_cores_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="cores")
     k_cores = [k[:nprompt].clone() for k in dec.kCache]
-    m["prefill_buckets_ms_per_prompt_token"] = prefill("buckets")
+    m["prefill_buckets_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="buckets")
     cos = [float(torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), k[:nprompt].double().reshape(1, -1))) for a, k in zip(k_cores, dec.kCache)]
     m["k_cache_cosine_buckets_vs_dense_cores"] = {"first_layer": cos[0], "last_layer": cos[-1], "min": min(cos), "mean": sum(cos) / len(cos)}
     m["buckets_over_cores_time"] = round(m["prefill_buckets_ms_per_prompt_token"] / m["prefill_cores_ms_per_prompt_token"], 3)
@@ -768,7 +708,7 @@ def prefill_buckets(b, res):
     torch.cuda.synchronize()
     m["model_memory_allocated_with_cores_GB"] = round(mem_with / 1e9, 3)
     m["model_memory_allocated_without_cores_GB"] = round((mem_with - (before - torch.cuda.memory_allocated())) / 1e9, 3)
-    m["prefill_buckets_without_cores_ms_per_prompt_token"] = prefill("buckets")
+    m["prefill_buckets_without_cores_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="buckets")
     out["model"] = m
     res["prefill_buckets"] = out
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
@@ -799,29 +739,6 @@ def prefill_attention(b, res):
     gen.manual_seed(78)
     heads, hd, maxTokens, pairs = 32, 128, 8192, 4
 
-    def us_per_call(fn, calls):
-        g._bind_stream()
-        fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        B._GRAPHS_FOR_LIFE.append(gr)
-        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-            fn()
-        g._bind_stream()
-        for _ in range(3):
-            gr.replay()
-        torch.cuda.synchronize()
-        best = float("inf")
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(4):
-                gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) * 1e3 / (4 * calls))
-        return best
-
     rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
     caches = [(rnd(maxTokens, heads, hd), rnd(maxTokens, heads, hd)) for _ in range(pairs)]
     q, out = rnd(64, heads * hd), torch.zeros((64, heads * hd), device=b.dev)
@@ -841,7 +758,7 @@ def prefill_attention(b, res):
                  "attention_block": sum(min(pos0 + rows, ((pos0 + min(16 * t + 15, rows - 1)) // 16 + 1) * 16) for t in range((rows + 15) // 16))}
         row = {}
         for name, entry in (("attention_rows", lib.effort_attention_rows), ("attention_block", lib.effort_attention_block)):
-            us = us_per_call(leg(entry, name, pos0, rows), pairs)
+            us = us_per_call(b, leg(entry, name, pos0, rows), pairs)
             row[name] = {"us_per_call": round(us, 2), "kv_bytes": asked[name] * rowBytes, "TBps_of_kv_bytes": round(asked[name] * rowBytes / us / 1e6, 3)}
         row["rows_over_block_time"] = round(row["attention_rows"]["us_per_call"] / row["attention_block"]["us_per_call"], 2)
         row["rows_over_block_bytes"] = round(asked["attention_rows"] / asked["attention_block"], 2)
@@ -857,16 +774,8 @@ def prefill_attention(b, res):
         dec = Decoder(model, maxTokens=nprompt + 8)
         prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
         for attention in ("rows", "block", "rows"):                              # (the rows path twice: its own run-to-run spread)
-            dec.prefill(prompt, chunk=64, attention=attention)
-            best = float("inf")
-            for _ in range(3):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                dec.prefill(prompt, chunk=64, attention=attention)
-                torch.cuda.synchronize()
-                best = min(best, time.perf_counter() - t0)
             key = f"prompt_{nprompt}_{attention}_ms_per_prompt_token"
-            m[key + "_again" if key in m else key] = round(best * 1e3 / nprompt, 4)
+            m[key + "_again" if key in m else key] = timed_prefill(b, dec, prompt, chunk=64, attention=attention)
         m[f"prompt_{nprompt}_rows_over_block"] = round(m[f"prompt_{nprompt}_rows_ms_per_prompt_token"] / m[f"prompt_{nprompt}_block_ms_per_prompt_token"], 3)
         del dec
         torch.cuda.empty_cache()

@@ -98,6 +98,8 @@ _SIGS = {
     "effort_weights_bucket_dense_ok": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "effort_bucket_gemm_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "effort_bucket_gemm_rows_routed": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int]),
+    "effort_weights_q4_dense_ok": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "effort_q4_gemm_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "effort_moe_route_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "effort_mix2_add_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int]),
     "effort_fetch_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int]),

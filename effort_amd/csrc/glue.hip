@@ -240,6 +240,56 @@ extern "C" int effort_bucket_gemm_rows_routed(effort_ctx* c, const effort_w* w, 
     return HIP_RC(c, launch_bucket_gemm_rows_routed(w->buckets, w->rowPitch, w->numExperts, idx2, x, (uint32_t)xPerSlot, c->d_xhRouted.buf, c->d_routedPart.buf,
                                               c->d_routedGroups.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
 }
+// ---- the block multiply on the Q4 buckets (prefill_q4.hip): the twins of the two plain entry points above, same refusal order, same scratch.
+// What a handle must be before it is looked at: Q4 (else EFFORT_ERR_KIND), no column shard, inDim % 32 == 0, a shape the core kernel serves.
+static int q4_handle_shape(const effort_w* w, const char* name) {
+    char what[128];
+    if (w->fmt != kQ4) { snprintf(what, sizeof(what), "%s: a Q4 bundle (FP16 buckets go through effort_bucket_gemm_rows)", name); return fail(w->ctx, EFFORT_ERR_KIND, what); }
+    if (w->view || w->inDim % 32u || !dense_gemm_rows_supported(w->inDim, w->outDim)) {
+        snprintf(what, sizeof(what), "%s: a full handle (no column shard), inDim %% 32 == 0", name);
+        return fail(w->ctx, EFFORT_ERR_SHAPE, what);
+    }
+    return EFFORT_OK;
+}
+// The handle's answer to "un-bucketable?", computed on first use (one kernel over the buckets and the stats, which also writes the
+// compact f16 means the multiply reads; synchronises) and kept until a refresh.  The means are (re)written IN PLACE.
+static int q4_dense_state(const effort_w* w, int* ok) {
+    effort_ctx* c = w->ctx;
+    if (w->q4Dense < 0) {
+        int bad[2] = {0, 0};
+        hipSetDevice(c->device);
+        JOIN_TRY(c);
+        if (!w->q4Means16) HIP_TRY(c, hipMalloc(&w->q4Means16, (size_t)w->numExperts * 8u * w->inDim * 2u));
+        HIP_TRY(c, hipMemsetAsync(c->d_status + 2, 0, 8, c->stream));
+        HIP_TRY(c, launch_q4_dense_check(w->buckets, w->rowPitch, w->cols, static_cast<const float*>(w->stats), w->inDim, w->numExperts, w->q4Means16,
+                                         c->d_status + 2, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bad, c->d_status + 2, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        w->q4Dense = bad[0] || bad[1] ? 0 : 1;
+    }
+    *ok = w->q4Dense;
+    return EFFORT_OK;
+}
+extern "C" int effort_weights_q4_dense_ok(effort_w* w, int* host_out) {
+    if (!w || !w->ctx || w->dead || !host_out) return EFFORT_ERR_ARG;
+    OK_TRY(q4_handle_shape(w, "weights_q4_dense_ok"));
+    return q4_dense_state(w, host_out);
+}
+extern "C" int effort_q4_gemm_rows(effort_ctx* c, const effort_w* w, int expert, const float* x, float* out, int rows) {
+    if (!w || w->dead) return fail(c, EFFORT_ERR_ARG, "q4_gemm_rows: null handle");
+    if (!prefill_rows_ok(rows) || expert < 0 || (uint32_t)expert >= w->numExperts) return fail(c, EFFORT_ERR_ARG, "q4_gemm_rows: 1 <= rows <= 64, 0 <= expert < numExperts");
+    OK_TRY(q4_handle_shape(w, "q4_gemm_rows"));
+    if (!c || c != w->ctx || !x || !out) return fail(c, EFFORT_ERR_ARG, "q4_gemm_rows: null argument (or a handle of another context)");
+    JOIN_TRY(c);
+    int ok = 0;
+    OK_TRY(q4_dense_state(w, &ok));
+    if (!ok) return fail(c, EFFORT_ERR_CONVERT, "q4_gemm_rows: the bundle is not un-bucketable (the ranks of a bucket do not name eight different outputs, or a row mean is no finite f16 number)");
+    OK_TRY(grow_block_scratch(c, w->inDim, w->outDim, rows, false));
+    const size_t row0 = (size_t)expert * 8u * w->inDim;
+    const uint16_t* B = reinterpret_cast<const uint16_t*>(reinterpret_cast<const unsigned char*>(w->buckets) + row0 * w->rowPitch);
+    return HIP_RC(c, launch_q4_gemm_rows(B, w->rowPitch, w->q4Means16 + row0, OutlierIndex{w->olBlockPtr, w->olEntry, w->olMeta}, x, c->d_xhRows.buf,
+                                         c->d_gemmPart.buf, out, w->inDim, w->outDim, (uint32_t)rows, c->stream));
+}
 extern "C" int effort_moe_route_rows(effort_ctx* c, const float* h, const void* normW, const void* gateW, int n, int numExperts, float* gateOut,
                                      uint32_t* idx2, float* val2, int rows) {
     if (n <= 0 || numExperts <= 0 || !prefill_rows_ok(rows)) return fail(c, EFFORT_ERR_ARG, "moe_route_rows: n, numExperts >= 1, 1 <= rows <= 64");

@@ -109,6 +109,8 @@ struct effort_w {
     float* rankBound = nullptr;       // [numExperts] fixed-point bound of the multiply (see launch_rank_bound)
     uint16_t* means16 = nullptr;      // FP16: the row means alone (stats lane .w), one u16 per bucket row (launch_compact_means)
     mutable int bucketDense = -1;     // effort_weights_bucket_dense_ok: -1 not checked yet, 0 two entries collide, 1 un-bucketable (effort_weights_refresh: -1 again)
+    mutable uint16_t* q4Means16 = nullptr;   // Q4: the row means as f16 (stats lane .y), one u16 per bucket row; written by effort_weights_q4_dense_ok's check, read by effort_q4_gemm_rows alone
+    mutable int q4Dense = -1;         // effort_weights_q4_dense_ok: -1 not checked yet, 0 not un-bucketable, 1 un-bucketable (effort_weights_refresh: -1 again)
     // Q4 outliers
     uint64_t nOutliers = 0;
     uint32_t* olBlockPtr = nullptr;   // entry bounds per block of 64 outputs (a column shard's: a slice of the full handle's)

@@ -1,7 +1,8 @@
-// What the two block multiplies of prompt prefill share: prefill.hip (the f16 cores) and prefill_buckets.hip (the bucketed weights,
-// un-bucketed on the fly).  Both walk K in stages of kPfStage under the SAME k split and reduce it with the same kernel, so that
-// the bucket kernel's bits are the core kernel's on the un-bucketed matrix.  The sequence of launches around the multiply is written
-// here once (pf_block_call); a launcher hands it the launch of its own kernel.  Read by glue.hip and the two prefill units alone.
+// What the block multiplies of prompt prefill share: prefill.hip (the f16 cores), prefill_buckets.hip (the FP16 bucketed weights,
+// un-bucketed on the fly) and prefill_q4.hip (the Q4 buckets, de-quantised on the fly).  All walk K in stages of kPfStage under the
+// SAME k split and reduce it with the same kernel, so that a bucket kernel's bits are the core kernel's on the un-bucketed matrix.
+// The sequence of launches around the multiply is written here once (pf_block_call); a launcher hands it the launch of its own
+// kernel.  Read by glue.hip and the three prefill units alone.
 #pragma once
 #include <type_traits>
 
@@ -107,5 +108,12 @@ hipError_t launch_bucket_gemm_rows(const uint16_t* B, uint32_t pitch, const floa
 hipError_t launch_bucket_gemm_rows_routed(const uint16_t* B, uint32_t pitch, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot,
                                           uint16_t* xh, float* part, uint32_t* groups, float* out, uint32_t inDim, uint32_t outDim, uint32_t rows,
                                           hipStream_t st);
+
+// prefill_q4.hip: the block multiply on the Q4 buckets, de-quantised on the fly, plus the handle's outliers; the scratch is the core
+// launcher's, same sizes.  B and means16 (the f16 row means launch_q4_dense_check writes) are ONE expert's.
+hipError_t launch_q4_dense_check(const uint16_t* B, uint32_t pitch, uint32_t words, const float* stats, uint32_t inDim, uint32_t numExperts,
+                                 uint16_t* means16, int* bad, hipStream_t st);
+hipError_t launch_q4_gemm_rows(const uint16_t* B, uint32_t pitch, const uint16_t* means16, const OutlierIndex& ol, const float* x, uint16_t* xh, float* part,
+                               float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
 
 }  // namespace effort

@@ -149,7 +149,7 @@ extern "C" int effort_weights_refresh(effort_w* w) {
     if (!w || !w->ctx || w->dead) return EFFORT_ERR_ARG;
     if (w->view) return fail(w->ctx, EFFORT_ERR_ARG, "effort_weights_refresh: a column shard takes its bound from the full handle -- refresh that one and shard again");
     hipSetDevice(w->ctx->device);
-    w->bucketDense = -1;                         // (effort_weights_bucket_dense_ok looks again)
+    w->bucketDense = w->q4Dense = -1;            // (effort_weights_bucket_dense_ok / effort_weights_q4_dense_ok look again)
     int rc = join_lanes(w->ctx);                 // multiplies still in flight on the lanes read what is recomputed here
     if (rc == EFFORT_OK) rc = register_bound(w->ctx, w);          // in place: graphs captured earlier keep valid pointers
     if (rc == EFFORT_OK && w->aligned) rc = copy_aligned(w);
@@ -212,7 +212,7 @@ extern "C" void effort_weights_free(effort_w* w) {
         if (w->views > 0) { w->dead = true; return; }
     }
     hipFree(w->olBlockPtr); hipFree(w->olEntry); hipFree(w->olMeta);
-    hipFree(w->aligned); hipFree(w->rankBound); hipFree(w->means16);
+    hipFree(w->aligned); hipFree(w->rankBound); hipFree(w->means16); hipFree(w->q4Means16);
     delete w;
 }
 

@@ -60,16 +60,18 @@ class Model:
 
     @classmethod
     def random(cls, cfg: MistralConfig, seed: int = 0, device="cuda", scale: float = 0.02, keep_cores: bool = True,
-               structured: bool = False, q4: bool = False) -> "Model":
+               structured: bool = False, q4: bool = False, q4_perc: float = 0.02) -> "Model":
         """Random-init weights of the architecture (no checkpoints here), converted by the GPU bucketizer.
         ``structured``: the statistics trained transformers show and i.i.d. Gaussians lack -- heavy-tailed weights with
         per-input-channel and per-output scale spread, norm weights with a few outlier channels (so the normalised state
         a multiply sees is heavy-tailed), a peaked output distribution -- see ``structured_matrix``.  The reference's quality
         figures (cos-sim 0.99 at 25 % effort, docs/ryc/ryc0.3.png) are for such weights; on Gaussian ones 25 % gives 0.94.
         ``q4``: the reference's Q4 model (q4_convert.py:48-66) from the SAME matrices the FP16 model of this seed has: wq, w1, w2
-        and w3 through the GPU Q4 converter (2 % outliers, cores kept), wk, wv and wo as cores only."""
-        if q4 and (cfg.numExperts > 1 or not keep_cores):
-            raise ValueError("Model.random(q4=True): Mistral only (one expert), cores kept -- wk, wv and wo ARE their cores")
+        and w3 through the GPU Q4 converter (the top ``q4_perc`` of the weights as outliers, 2 % by default), wk, wv and wo as cores
+        only -- they ARE their cores.  With ``keep_cores=False`` the four Q4 bundles drop their cores: the model decodes as ever and
+        prefills through ``Decoder.prefill(weights="q4")``."""
+        if q4 and cfg.numExperts > 1:
+            raise ValueError("Model.random(q4=True): Mistral only (one expert) -- wk, wv and wo ARE their cores")
         m = cls(cfg)
         gen = torch.Generator(device=device)
         gen.manual_seed(seed)
@@ -89,7 +91,9 @@ class Model:
         def bundle(o, i, experts=1, name=""):
             if q4:
                 core = mat(o, i)
-                return ExpertWeights.from_core_q4(core) if name in ("wq", "w1", "w2", "w3") else ExpertWeights.core_only(core, q4=True)
+                if name in ("wq", "w1", "w2", "w3"):
+                    return ExpertWeights.from_core_q4(core, q4_perc, keep_core=keep_cores)
+                return ExpertWeights.core_only(core, q4=True)
             ews = []
             for _ in range(experts):
                 ew = ExpertWeights.from_core(mat(o, i))
@@ -485,7 +489,7 @@ class Decoder:
             self.pf_gateOut = torch.zeros((cfg.numLayers, chunk, cfg.numExperts), dtype=torch.float32, device=dev)
         self._pf = chunk
 
-    def _block_multiplies(self, from_buckets: bool):
+    def _block_multiplies(self, from_buckets: bool, q4: bool = False):
         """The two block multiplies of a ``prefill`` walk, chosen once per call by ``weights``:
 
         ``mul(x, ew, out, rows)``: out[r] = M * f16(x[r]) for the first ``rows`` rows, ONE pass over the matrix;
@@ -496,7 +500,9 @@ class Decoder:
         (EFFORT_ERR_SHAPE: nothing was enqueued) goes to ``basicMul`` row by row, a stack to ``basicMulExpert`` per assignment, as
         ``_dense_experts`` falls back.  On the buckets M is the un-bucketed matrix of ``ew`` (effort_bucket_gemm_rows /
         effort_bucket_gemm_rows_routed): no core is read, and there is no fallback -- every refusal of the library was ruled out by
-        ``prefill`` before anything was enqueued, so one is an error."""
+        ``prefill`` before anything was enqueued, so one is an error.  ``q4`` (``weights="q4"``, dense FFN only) decides per bundle:
+        a Q4 bundle multiplies by ``unbucket_q4()`` of its buckets plus its outliers (effort_q4_gemm_rows, expert 0; no core is
+        read, no fallback), a core-only bundle goes the way of the cores."""
         g, lib = self.g, _lib.lib()
         if from_buckets:
             def mul(x, ew, out, rows):
@@ -525,6 +531,14 @@ class Decoder:
                         basicMulExpert(x[r][sl] if per_slot else x[r], cores, idx2[r][sl:sl + 1], out[r][sl])
                 return
             g.check(rc, "dense_gemm_rows_routed")
+        if q4:
+            core_mul = mul
+
+            def mul(x, ew, out, rows):                     # noqa: F811
+                if not ew.bucketsLoaded:
+                    return core_mul(x, ew, out, rows)
+                g.check(lib.effort_q4_gemm_rows(g.ctx, ew.handle, 0, _p(x), _p(out), rows), "q4_gemm_rows")
+            return mul, None
         return mul, mul_routed
 
     def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense",
@@ -561,9 +575,16 @@ class Decoder:
         low four mantissa bits of every weight replaced by its position in the bucket: the caches hold the K / V a decode at effort
         1.0 would write (up to the order of the sums and the f16 rounding of the inputs), not the dense path's -- bit for bit those of
         ``weights="cores"`` on a model whose cores are ``unbucket()`` of its buckets.  There is no row-by-row fallback: no core exists
-        to fall back to.
+        to fall back to.  ``"q4"`` is the path of a model with Q4 bundles (``Model.random(q4=True, keep_cores=False)``): per bundle, a
+        Q4 bundle multiplies by ``unbucket_q4()`` of its buckets -- the sign of every weight times the mean of its bucket row -- plus
+        its outliers on the f32 input (effort_q4_gemm_rows), a core-only bundle (wk, wv, wo) by its core.  No core of a Q4 bundle is
+        looked at, and the caches hold the K / V a Q4 decode at effort 1.0 would write, not the dense ones: a Q4 weight differs from
+        its core by the whole quantisation.  Every Q4 handle is asked once whether it is un-bucketable
+        (effort_weights_q4_dense_ok).  Dense FFN only.
 
-        Raises ValueError, before anything is enqueued: a ``weights`` other than ``"cores"`` / ``"buckets"``; under ``"buckets"`` a Q4
+        Raises ValueError, before anything is enqueued: a ``weights`` other than ``"cores"`` / ``"buckets"`` / ``"q4"``; under ``"q4"``
+        an FP16 bucketed bundle (``"buckets"`` is its path), a core-only bundle without its core, a Q4 bundle that is not
+        un-bucketable and ``ffn="routed"``; under ``"buckets"`` a Q4
         or core-only bundle, a bundle truncated below ``percentLoad`` 16 and one that is not un-bucketable; a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
         ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"``, an ``ffn`` other
@@ -573,9 +594,11 @@ class Decoder:
         T = len(ids)
         if ffn not in ("dense", "routed"):
             raise ValueError(f"Decoder.prefill: ffn must be 'dense' or 'routed', not {ffn!r}")
-        if weights not in ("cores", "buckets"):
-            raise ValueError(f"Decoder.prefill: weights must be 'cores' or 'buckets', not {weights!r}")
-        routed, from_buckets = ffn == "routed", weights == "buckets"
+        if weights not in ("cores", "buckets", "q4"):
+            raise ValueError(f"Decoder.prefill: weights must be 'cores' or 'buckets', not {weights!r} (or 'q4', for a model with Q4 bundles)")
+        routed, from_buckets, from_q4 = ffn == "routed", weights == "buckets", weights == "q4"
+        if from_q4 and routed:
+            raise ValueError("Decoder.prefill: weights='q4' serves ffn='dense' alone (the reference writes no Q4 Mixtral model)")
         if routed and not (cfg.numExperts >= 2 and all(L.ffnGate is not None and L.ffnGate.dtype == torch.float16 for L in m.layers)):
             raise ValueError("Decoder.prefill: ffn='routed' is for Mixtral models (an f16 ffnGate in every layer, numExperts >= 2)")
         if not routed and (self.moe or cfg.numExperts > 1):
@@ -590,6 +613,11 @@ class Decoder:
                 raise ValueError("Decoder.prefill: weights='buckets' needs percentLoad 16 (a truncated bundle does not hold the whole matrix)")
             if routed and any(getattr(L, w).numExperts != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
                 raise ValueError("Decoder.prefill: ffn='routed' needs the expert stacks [numExperts] (w1, w2, w3)")
+        elif from_q4:
+            if any(ew.bucketsLoaded and not ew.q4 for ew in bundles):
+                raise ValueError("Decoder.prefill: weights='q4' is for Q4 and core-only bundles (an FP16 bucketed bundle prefills with weights='buckets')")
+            if any(not ew.bucketsLoaded and ew.core is None for ew in bundles):
+                raise ValueError("Decoder.prefill: weights='q4' needs the f16 core of every core-only bundle (wk, wv, wo)")
         elif any(ew.core is None for ew in bundles):
             raise ValueError("Decoder.prefill: every bundle needs its f16 core (Model.random(keep_cores=True), or a Q4 model)")
         if routed and not from_buckets and any(getattr(L, w).core.dim() != 3 or int(getattr(L, w).core.shape[0]) != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
@@ -610,10 +638,19 @@ class Decoder:
                 if not ok.value:
                     raise ValueError("Decoder.prefill: weights='buckets' needs un-bucketable bundles (two entries of one bucket name the same output: "
                                      "the converter reported drops)")
+        if from_q4:                                        # (as above: each Q4 handle's buckets and means are looked at once)
+            for ew in bundles:
+                if not ew.bucketsLoaded:
+                    continue
+                ok = C.c_int(0)
+                g.check(lib.effort_weights_q4_dense_ok(ew.handle, C.byref(ok)), "weights_q4_dense_ok")
+                if not ok.value:
+                    raise ValueError("Decoder.prefill: weights='q4' needs un-bucketable Q4 bundles (the ranks of every bucket name eight different "
+                                     "outputs, every row mean is a finite f16 number)")
         self._prefill_buffers(chunk)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
         rope = C.c_float(cfg.ropeBase)
-        mul, mul_routed = self._block_multiplies(from_buckets)
+        mul, mul_routed = self._block_multiplies(from_buckets, from_q4)
         for b0 in range(0, T, chunk):
             rows, p = min(chunk, T - b0), pos0 + b0
             self.pf_ids[:rows].copy_(torch.tensor(ids[b0:b0 + rows], dtype=torch.int32))
@@ -691,8 +728,9 @@ class Decoder:
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
         ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
-        ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"``: a
-        model without cores prefills only with ``"buckets"``, and its caches then hold effort-1.0 K / V, not dense ones).
+        ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
+        FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
+        and the caches then hold effort-1.0 K / V, not dense ones).
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens

@@ -55,6 +55,52 @@ def unbucket(buckets: torch.Tensor, inSize: int, outSize: int) -> torch.Tensor:
     return out.view(torch.float16)
 
 
+def unbucket_q4(buckets: torch.Tensor, stats: torch.Tensor, inSize: int, outSize: int) -> torch.Tensor:
+    """The UN-BUCKETED matrix U4 of Q4 buckets -- f16 [E, outSize, inSize] -- in torch ops, on the host or the device the buckets
+    live on.  ``buckets`` is [E, 8 * inSize, outSize / 32] (or one expert's 2-d tensor) of 16-bit words, ``stats`` f32
+    [E, 8 * inSize, 2].
+
+    Bucket row i = 8 j + r holds rank r of input j.  Word x of a row holds four nibbles, the first in bits 15 .. 12; nibble n
+    (0 = highest) is sign << 3 | pos and names output 32 x + 8 n + pos.  U4[e][32 x + 8 n + pos][j] = +-f16(m), m = stats[e][i][1]
+    -- the second lane, the one prepareDispatchQ4 reads --, + for a clear sign bit: a weight that was zero counts as +m, as the
+    reference's Metal kernel treats it (its Python draft gives 0).  Raises ValueError when the eight ranks of one (e, j, x, n) do not
+    name eight different positions, or when a mean is not a finite f16 number stored as f32: such a bundle holds no matrix to
+    return.  The Q4 converter always writes bundles that do.
+
+    This is the specification of what ``Decoder.prefill(weights="q4")`` multiplies a Q4 bundle by, before the outliers."""
+    inSize, outSize = int(inSize), int(outSize)
+    if buckets.element_size() != 2:
+        raise ValueError("unbucket_q4: buckets of 16-bit words")
+    b = buckets.view(torch.int16)
+    if b.dim() == 2:
+        b = b.unsqueeze(0)
+    words = outSize // 32
+    if outSize % 32 or b.dim() != 3 or b.shape[1] != 8 * inSize or b.shape[2] < words:
+        raise ValueError(f"unbucket_q4: buckets [E, {8 * inSize}, >= {words}] expected, got {tuple(b.shape)}")
+    E = b.shape[0]
+    if stats.dtype != torch.float32 or stats.numel() != E * 8 * inSize * 2:
+        raise ValueError(f"unbucket_q4: stats f32 [E, {8 * inSize}, 2] expected, got {stats.dtype} {tuple(stats.shape)}")
+    m = stats.reshape(E, inSize, 8, 2)[..., 1].to(b.device)
+    m16 = m.to(torch.float16)
+    if not bool(torch.isfinite(m).all()) or not bool((m16.to(torch.float32) == m).all()):
+        raise ValueError("unbucket_q4: a row mean (stats lane 1) is not a finite f16 number stored as f32 -- the bundle is not un-bucketable")
+    mbits = m16.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF                       # [E][j][r]
+    out = torch.empty((E, outSize, inSize), dtype=torch.int16, device=b.device)
+    for e in range(E):
+        w = b[e, :, :words].reshape(inSize, 8, words).to(torch.int32) & 0xFFFF                 # [j][r][x]
+        nib = torch.stack([(w >> 12) & 15, (w >> 8) & 15, (w >> 4) & 15, w & 15], dim=-1)      # [j][r][x][n]
+        val = mbits[e][:, :, None, None] ^ ((nib >> 3) << 15)
+        pos = (nib & 7).permute(0, 2, 3, 1).contiguous().to(torch.int64)                       # [j][x][n][r]
+        val = val.permute(0, 2, 3, 1).contiguous()
+        named = torch.zeros((inSize, words, 4, 8), dtype=torch.int32, device=b.device).scatter_add_(3, pos, torch.ones_like(val))
+        if bool((named != 1).any()):
+            raise ValueError("unbucket_q4: the eight ranks of a bucket do not name eight different positions -- the bundle is not un-bucketable")
+        u = torch.zeros((inSize, words, 4, 8), dtype=torch.int32, device=b.device).scatter_add_(3, pos, val)
+        u = ((u ^ 0x8000) - 0x8000).to(torch.int16)            # the 16-bit pattern as int16
+        out[e] = u.reshape(inSize, outSize).t()
+    return out.view(torch.float16)
+
+
 class ExpertWeights:
     def __init__(self, buckets: torch.Tensor, stats: torch.Tensor, probes: torch.Tensor, inSize: int, outSize: int,
                  percentLoad: int | None = None, numExperts: int = 1, outliers: torch.Tensor | None = None,
@@ -164,14 +210,15 @@ class ExpertWeights:
         return ew
 
     @classmethod
-    def from_core_q4(cls, core: torch.Tensor, perc: float = 0.02) -> "ExpertWeights":
+    def from_core_q4(cls, core: torch.Tensor, perc: float = 0.02, keep_core: bool = True) -> "ExpertWeights":
         """Dense f16 matrix [outSize, inSize] -> Q4 bundle via the GPU Q4 converter (q4_convert.py:54,63: convert(W.T)), the
-        top ``perc`` of the weights kept as outliers, the core kept."""
+        top ``perc`` of the weights kept as outliers.  ``keep_core=False`` drops the f16 core: the bundle then decodes as ever and
+        prefills through ``Decoder.prefill(weights="q4")`` alone."""
         from .q4 import convert
         t = convert(core.t().contiguous(), perc)
         outl = t["outliers"] if t["outliers"].shape[0] else None
         return cls(t["buckets"], t["bucket.stats"], t["probes"], inSize=core.shape[1], outSize=core.shape[0], outliers=outl,
-                   core=core, q4=True)
+                   core=core if keep_core else None, q4=True)
 
     @classmethod
     def stack(cls, experts: list["ExpertWeights"]) -> "ExpertWeights":
@@ -194,6 +241,13 @@ class ExpertWeights:
         if self.q4 or not self.bucketsLoaded or self.percentLoad != 16:
             raise ValueError("ExpertWeights.unbucket: an FP16 bundle with its buckets loaded at percentLoad 16")
         return unbucket(self.buckets, self.inSize, self.outSize)
+
+    def unbucket_q4(self) -> torch.Tensor:
+        """``unbucket_q4`` of this bundle's buckets and stats: f16 [numExperts, outSize, inSize], the matrix
+        ``Decoder.prefill(weights="q4")`` multiplies by before it adds the outliers.  Q4 bundles with their buckets loaded only."""
+        if not self.q4 or not self.bucketsLoaded:
+            raise ValueError("ExpertWeights.unbucket_q4: a Q4 bundle with its buckets loaded")
+        return unbucket_q4(self.buckets, self.stats, self.inSize, self.outSize)
 
     def align_rows(self) -> int:
         """For bundles held in the reference's dense layout (loaded from a file, ``from_core(aligned=False)``): give the handle

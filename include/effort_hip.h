@@ -428,6 +428,35 @@ EFFORT_API int effort_weights_bucket_dense_ok(effort_w* w, int* host_out);
 EFFORT_API int effort_bucket_gemm_rows(effort_ctx* ctx, const effort_w* w, int expert, const float* x_dev, float* out_dev, int rows);
 EFFORT_API int effort_bucket_gemm_rows_routed(effort_ctx* ctx, const effort_w* w, const uint32_t* idx2_dev, const float* x_dev, int xPerSlot,
                                    float* out_dev, int rows);
+/* Prompt prefill straight from the Q4 buckets (csrc/prefill_q4.hip): the Q4 twins of the two plain entry points above, so that a Q4
+ * model prefills with no f16 core of a Q4 bundle in memory.  The matrix U4 of a registered Q4 handle:
+ *   bucket row i = 8 j + r of expert e holds rank r of input j, outDim / 32 16-bit words; word x holds four nibbles, the first in bits
+ *   15 .. 12; nibble n = sign << 3 | pos names output 32 x + 8 n + pos, and U4[e][32 x + 8 n + pos][j] = +-f16(m) with m = stats[i].y
+ *   (the second lane of the f32 x 2 stats, what prepareDispatchQ4 reads), a clear sign bit +: a zero weight counts as +m.
+ * A Q4 bundle is UN-BUCKETABLE iff for every (e, j, x, n) the eight ranks name eight different positions and every stats[i].y is a
+ * finite f16 number stored as f32; every element of U4 is then named exactly once.  The converter always writes such bundles;
+ * others are refused (EFFORT_ERR_CONVERT), never guessed at.  A prefill through these calls writes the K / V a Q4 decode at effort
+ * 1.0 would write (up to the order of the sums and the f16(x) rounding), NOT the dense path's.
+ *
+ * effort_weights_q4_dense_ok: *host_out = 1 when the handle is un-bucketable, 0 when not.  One kernel over the buckets and lane .y
+ * of the stats, which also writes the handle's compact f16 copy of the means (what the multiply reads); synchronises.  The answer is
+ * cached on the handle; effort_weights_refresh clears it.  The multiply runs it itself on a handle's first use.
+ *
+ * effort_q4_gemm_rows: out[r] = U4[expert] * f16(x[r]) + sum over the handle's outliers k on that output of val_k * x[r][in_k], for
+ * r < rows, x f32 [rows][inDim], out f32 [rows][outDim].  CONTRACT: for a handle without outliers BIT FOR BIT what
+ * effort_dense_gemm_rows writes when U4[expert] is given to it as W, so that entry's contract holds word for word.  The outlier term
+ * uses the f32 x (calcOutliers, bucketMulQ4.metal:13-21) and is added to the product in f32, one fmaf per outlier in the order of the
+ * handle's outlier index (an output's entries in table order): a function of the handle and of row r alone, never of rows.  A bucket
+ * row is read only inside its outDim / 16 payload bytes, lane .y of the stats only through the compact copy, other experts' rows not
+ * at all.  One more launch than effort_bucket_gemm_rows when the handle has outliers, none otherwise.
+ *
+ * Refusals, nothing enqueued on any of them, values before pointers: rows outside 1 .. 64, expert outside 0 .. numExperts - 1, a NULL
+ * handle: EFFORT_ERR_ARG; an FP16 handle: EFFORT_ERR_KIND; a column shard, inDim % 32 != 0, a shape effort_dense_gemm_rows refuses:
+ * EFFORT_ERR_SHAPE; then a NULL pointer (or a context other than the handle's): EFFORT_ERR_ARG; then, the lanes joined, a bundle that
+ * is not un-bucketable: EFFORT_ERR_CONVERT.  SCRATCH: effort_dense_gemm_rows's.  No routed form: the reference writes no Q4 Mixtral
+ * model.  effort_weights_bucket_dense_ok and effort_bucket_gemm_rows keep answering EFFORT_ERR_KIND for Q4 handles. */
+EFFORT_API int effort_weights_q4_dense_ok(effort_w* w, int* host_out);
+EFFORT_API int effort_q4_gemm_rows(effort_ctx* ctx, const effort_w* w, int expert, const float* x_dev, float* out_dev, int rows);
 /* Block forms of the Mixtral glue, per row BIT FOR BIT the token forms (the same body):
  * effort_moe_route_rows: effort_moe_route on row r of h [rows][n]; idx2 / val2 [rows][2], gate_out (may be NULL) [rows][numExperts].
  * effort_mix2_add_rows: effort_mix2_add on row r of h [rows][n] with f0 = f[r][0], f1 = f[r][1] (f f32 [rows][2][n]) and val2[r]. */

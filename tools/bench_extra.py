@@ -13,7 +13,9 @@ record also goes to profiles/r09_prefill.json; asked for alone, it skips the hea
 both attention paths; its record also goes to profiles/r10_prefill_attention.json; standalone like `decode_prefill`) and
 `prefill_mixtral` (a Mixtral prompt: the routed block multiply beside 8 dense block calls, and Decoder.prefill(ffn="routed") beside the
 token loop; its record also goes to profiles/r11_prefill_mixtral.json; standalone too) and `prefill_buckets` (prefill straight from the
-bucketed weights beside the core kernel in the same run; its record also goes to profiles/r12_prefill_buckets.json; standalone too).
+bucketed weights beside the core kernel in the same run; its record also goes to profiles/r12_prefill_buckets.json; standalone too) and
+`prefill_q4` (prefill straight from the Q4 buckets beside the core and the FP16 bucket kernel in the same run, and whose K caches a Q4
+decode agrees with; its record also goes to profiles/r13_prefill_q4.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -31,8 +33,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets")             # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -718,6 +720,118 @@ def prefill_buckets(b, res):
     del dec, model
 
 
+def prefill_q4(b, res):
+    """Prefill straight from the Q4 buckets (effort_q4_gemm_rows: the block multiply de-quantising on the fly, then the outlier pass)
+    beside the core kernel and the FP16 bucket kernel MEASURED IN THE SAME RUN.  Kernel legs, prefill_buckets' protocol (rotating
+    disjoint matrices, more than 768 MB of f16 cores per shape, one pass per graph, best of 3 windows): us per call at 16 and 64 rows
+    on the decode loop's four shapes; the Q4 bundles are the converter's (2 % outliers), and the same buckets registered WITHOUT their
+    outliers give the multiply alone.  (A Q4 matrix is a quarter of its core: the rotating Q4 set is that much smaller.)  Model legs,
+    the reference's Q4 model at Mistral-7B shapes, a 256-token prompt: `Decoder.prefill` ms per prompt token with ``weights="cores"``
+    and ``weights="q4"``; the cosine of the layer-0 and last-layer K caches of either prefill against those a token-by-token Q4 decode
+    at effort 1.0 writes; ``torch.cuda.memory_allocated`` with and without the Q4 bundles' cores -- after which the prompt is prefilled
+    once more."""
+    import ctypes as C
+    import gc
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    from effort_amd.q4 import convert as q4_convert
+    from effort_amd.weights import ExpertWeights
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(78)
+
+    kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events; all kernels in this run; "
+                        "a workgroup of the Q4 kernel owns 16 words of every bucket row (32 bytes, 512 outputs); q4 = multiply + outlier pass "
+                        "(2 % outliers), q4_no_outliers = the same buckets registered without them"}
+    for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
+        nbytes = outD * inD * 2
+        count = max(4, -(-(768 << 20) // nbytes))
+        cores = [(torch.randn((outD, inD), generator=gen, device=b.dev, dtype=torch.float32) * 0.02).to(torch.float16) for _ in range(count)]
+        fp16 = [ExpertWeights.from_core(c) for c in cores]
+        def q4_bundle(core):                                                     # from_core_q4; a matrix of fewer than 4096 outputs (wk, wv: never
+            t = q4_convert(core.t().contiguous(), 0.02)                          # Q4 in the reference's model) gets its probes padded: prefill reads none
+            probes = torch.zeros(4096, dtype=torch.float16, device=b.dev)
+            probes[:t["probes"].numel()] = t["probes"]
+            return ExpertWeights(t["buckets"], t["bucket.stats"], probes, inD, outD, outliers=t["outliers"], q4=True)
+        q4 = [q4_bundle(c) for c in cores]
+        bare =[ExpertWeights(e.buckets, e.stats, e.probes, inD, outD, None, 1, q4=True) for e in q4]
+        for ew in fp16 + q4 + bare:
+            ew.handle
+        x = torch.randn((64, inD), generator=gen, device=b.dev, dtype=torch.float32)
+        out = torch.zeros((64, outD), device=b.dev)
+
+        def leg(kind, rows):
+            def fn():
+                g._bind_stream()
+                for i in range(count):
+                    if kind == "core":
+                        g.check(lib.effort_dense_gemm_rows(g.ctx, p(cores[i]), p(x), p(out), inD, outD, rows), "dense_gemm_rows")
+                    elif kind == "bucket":
+                        g.check(lib.effort_bucket_gemm_rows(g.ctx, fp16[i].handle, 0, p(x), p(out), rows), "bucket_gemm_rows")
+                    else:
+                        g.check(lib.effort_q4_gemm_rows(g.ctx, (q4 if kind == "q4" else bare)[i].handle, 0, p(x), p(out), rows), "q4_gemm_rows")
+            return fn
+        row = {"matrices": count, "core_bytes": nbytes, "q4_bucket_bytes": nbytes // 4, "outliers": int(q4[0].outliers.shape[0])}
+        for rows in (16, 64):
+            for kind in ("core", "bucket", "q4", "q4_no_outliers"):
+                row[f"{kind}_rows_{rows}"] = {"us_per_call": round(us_per_call(b, leg(kind, rows), count), 2)}
+            for kind in ("bucket", "q4", "q4_no_outliers"):
+                row[f"{kind}_over_core_time_{rows}"] = round(row[f"{kind}_rows_{rows}"]["us_per_call"] / row[f"core_rows_{rows}"]["us_per_call"], 3)
+        kern[f"{inD}->{outD}"] = row
+        del cores, fp16, q4, bare, x, out
+        gc.collect()
+        torch.cuda.empty_cache()
+    out = {"kernel": kern}
+
+    nprompt = 256
+    model = Model.random(MistralConfig(), seed=1, q4=True)
+    torch.cuda.synchronize()
+    mem_with = torch.cuda.memory_allocated()
+    dec = Decoder(model, maxTokens=nprompt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+    cosine = lambda a, k: float(torch.nn.functional.cosine_similarity(a.double().reshape(1, -1), k.double().reshape(1, -1)))      # noqa: E731
+    ends = lambda: [dec.kCache[n][:nprompt].clone() for n in (0, len(dec.kCache) - 1)]                                               # noqa: E731
+
+    m = {"model": "the reference's Q4 model (wq, w1, w2, w3 in Q4 with 2 % outliers; wk, wv, wo cores) at Mistral-7B shapes, 32 layers, random weights, seed 1",
+         "prompt_tokens": nprompt,
+         "protocol": "eager, synchronised wall time of Decoder.prefill(chunk=64) over the whole prompt, best of 3 after a warm call; the decode: the "
+                     "prompt token by token through the captured step at effort 1.0"}
+    m["prefill_cores_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="cores")
+    k_cores = ends()
+    m["prefill_q4_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="q4")
+    k_q4 = ends()
+    m["q4_over_cores_time"] = round(m["prefill_q4_ms_per_prompt_token"] / m["prefill_cores_ms_per_prompt_token"], 3)
+    dec.run(prompt, nprompt, effort=1.0)
+    torch.cuda.synchronize()
+    k_dec = ends()
+    m["k_cache_cosine_against_q4_decode_at_effort_1"] = {
+        "q4_prefill": {"first_layer": cosine(k_q4[0], k_dec[0]), "last_layer": cosine(k_q4[1], k_dec[1])},
+        "cores_prefill": {"first_layer": cosine(k_cores[0], k_dec[0]), "last_layer": cosine(k_cores[1], k_dec[1])}}
+    before = torch.cuda.memory_allocated()
+    for L in model.layers:
+        for w in ("wq", "w1", "w2", "w3"):
+            getattr(L, w).core = None
+    gc.collect()
+    torch.cuda.synchronize()
+    m["model_memory_allocated_with_q4_cores_GB"] = round(mem_with / 1e9, 3)
+    m["model_memory_allocated_without_q4_cores_GB"] = round((mem_with - (before - torch.cuda.memory_allocated())) / 1e9, 3)
+    m["prefill_q4_without_q4_cores_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, weights="q4")
+    out["model"] = m
+    res["prefill_q4"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r13_prefill_q4.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def prefill_attention(b, res):
     """Prefill attention: effort_attention_rows (every query of a block reads K / V again) beside effort_attention_block (the block's
     queries share each K / V tile), one process.  Kernel legs, decode_prefill's protocol: 32 heads, headDim 128, maxTokens 8192, a pass
@@ -807,7 +921,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
-       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets}
+       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4}
 
 
 class Light:

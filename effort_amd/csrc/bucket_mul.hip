@@ -754,6 +754,33 @@ __device__ __forceinline__ void mul_item(const GroupKArgs& ga, const uint32_t it
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<uint16_t*>((size_t)(uint32_t)__builtin_amdgcn_readfirstlane(vBuckLo) | ((size_t)(uint32_t)__builtin_amdgcn_readfirstlane(vBuckHi) << 32)), 0,     // (uint32_t: readfirstlane returns int, and a sign-extended low half is another pointer)
         (int)__builtin_amdgcn_readfirstlane(vRecords), 0x00020000);
+    // Q4, E > 1, a row whose LAST word is the first half of a dword of its piece (cols - 1 even modulo E: 32 outputs at E = 2 or 4, 96 at
+    // E = 2): on the LAST row of the buffer that dword straddles the end of the descriptor's records, the range check answers 0 for the
+    // whole of it, and the stream below adds the row's value for a ZERO word -- nibble 0 of the four sub-buckets -- in place of the word
+    // (tests/test_gpu_cutoff_paths.py: six outputs of 32 off by 1e-3 of max|out| once that row is kept).  The thread that kept that row
+    // reads the word with a 16-bit load of its own, takes the zero word's four adds back and makes the word's: integer adds on the same
+    // tile (zeroed before the barrier above), exact in any order.  One word of a whole handle: off the streaming loop.
+    if constexpr (FMT != kFp16 && E > 1) {
+        const uint32_t lastCol = g.cols - 1u, jw = lastCol % (uint32_t)E;
+        if (!(jw & 1u) && t == lastCol / (64u * (uint32_t)E) && !(GA_ABLATE(ga) & 4u)) {            // uniform
+            const uint32_t lastRow = g.numExperts * g.expertRows - 1u;
+            const uint32_t cL = lastRow - (e * g.expertRows + j0 * 8u);                             // that row as a slot of this slice (wraps past nSlots elsewhere)
+            const size_t offL = (size_t)lastRow * g.rowPitch + (size_t)lastCol * 2u;                // its last word; the dword from there on ends past the records
+            if (cL < nSlots && offL + 2u <= (size_t)vRecords && offL + 4u > (size_t)vRecords) {     // uniform
+                if ((uint32_t)tid == cL % (uint32_t)NT && ((keepMask >> (cL / (uint32_t)NT)) & 1u)) {
+                    const uint32_t x = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (uint32_t)offL, 0u, 0);
+                    const int di = __float2int_rn((vblk[cL >> 3] * means[cL]) * scale);            // (decode_code's value of the row)
+                    const uint32_t laneP = (lastCol / (uint32_t)E) & 63u;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const uint32_t nib = (x >> (4 * q)) & 15u, plane = (uint32_t)((3 - q) * 16 * E);
+                        atomicAdd(&acc[laneP + 64u * (jw + (uint32_t)E * nib + plane)], di);
+                        atomicSub(&acc[laneP + 64u * (jw + plane)], di);
+                    }
+                }
+            }
+        }
+    }
     const uint32_t nU = (GA_ABLATE(ga) & 4u) ? 0u : __builtin_amdgcn_readfirstlane(n);   // n is workgroup-uniform; keep it in an SGPR
     // The waves of a workgroup do NOT run at one speed (the older wave wins the arbitration for issue slots and the memory
     // pipeline: measured, wave 0 gets through a static share of the rows 2-3x sooner than the last wave and then idles at

@@ -24,6 +24,9 @@ def __getattr__(name):
     if name in ("Sampling", "philox_u", "sample_reference"):
         from . import sampling as _sm
         return getattr(_sm, name)
+    if name in ("Rules", "rules_reference"):
+        from . import rules as _r
+        return getattr(_r, name)
     if name == "bucketize":
         from . import convert as _c
         return _c.bucketize

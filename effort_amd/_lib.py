@@ -84,6 +84,7 @@ _SIGS = {
     "effort_sample": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
     "effort_topk": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "effort_sample_bits": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "effort_logit_rules": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "effort_convert_status": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "effort_q4_outlier_count": (C.c_int64, [C.c_int, C.c_int, C.c_double]),
     "effort_convert_q4": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),

@@ -280,6 +280,10 @@ hipError_t launch_sample(const float* logits, uint32_t n, const void* params, ui
                          int* status, uint32_t* topkIdx, float* topkVal, hipStream_t st);
 hipError_t launch_topk(const float* logits, uint32_t n, uint32_t k, uint32_t* idx, float* val, hipStream_t st);
 
+// the generation rules in front of the pick (rules.hip)
+hipError_t launch_rules(const float* in, uint32_t n, const void* params, const uint32_t* tok, const uint32_t* pos, uint32_t* seq, uint32_t seqLen,
+                        const uint32_t* biasIds, const float* biasVals, uint32_t* stopPos, float* out, int* status, hipStream_t st);
+
 hipError_t launch_f32_to_f16(const float* in, uint16_t* out, uint32_t n, hipStream_t st);
 hipError_t launch_cosine(const float* a, const float* b, uint32_t n, float* out3, hipStream_t st);
 hipError_t launch_validate_outliers(const float* outliers, uint64_t n, uint32_t inDim, uint32_t outDim, int* bad, hipStream_t st);

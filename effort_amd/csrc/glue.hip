@@ -392,6 +392,16 @@ extern "C" int effort_topk(effort_ctx* c, const float* logits, int n, int k, uin
     JOIN_TRY(c);
     return HIP_RC(c, launch_topk(logits, (uint32_t)n, (uint32_t)k, idx, val, c->stream));
 }
+// The generation rules (rules.hip), between the LM head and the pick.  Their settings, too, are read on the device.
+extern "C" int effort_logit_rules(effort_ctx* c, const float* logitsIn, int n, const effort_rules_params* params, const uint32_t* tok, const uint32_t* pos,
+                                  uint32_t* seq, int seqLen, const uint32_t* biasIds, const float* biasVals, uint32_t* stopPos, float* logitsOut) {
+    if (!c || n < 1 || seqLen < 0) return fail(c, EFFORT_ERR_ARG, "logit_rules: bad argument (n >= 1, seqLen >= 0)");
+    if (!logitsIn || !logitsOut || !params || !pos) return fail(c, EFFORT_ERR_ARG, "logit_rules: null argument");
+    if (!tok != !seq || !biasIds != !biasVals) return fail(c, EFFORT_ERR_ARG, "logit_rules: tok and seq, bias ids and values come in pairs");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rules(logitsIn, (uint32_t)n, params, tok, pos, seq, (uint32_t)seqLen, biasIds, biasVals, stopPos, logitsOut, c->d_status + 1,
+                                  c->stream));
+}
 extern "C" uint32_t effort_sample_bits(uint32_t seedLo, uint32_t seedHi, uint32_t stream, uint32_t pos) { return philox_x0(seedLo, seedHi, stream, pos); }
 
 // ---- status words: conditions the device could not report through a return code.  Each is read and cleared. ----

@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from .bucket_mul import basicMul, basicMulExpert, bucketMul, bucketMulGroup, bucketMulQ4
+from .rules import Rules
 from .runtime import gpu as _gpu
 from .sampling import Sampling
 from .weights import ExpertWeights
@@ -271,9 +272,11 @@ class Decoder:
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
         self._pf = None                                   # prefill's block buffers: made by the first ``prefill`` (see ``_prefill_buffers``)
         self.last_prefill_s = None                        # run(prefill=True): synchronised wall time of its prefill
+        self._rules = False                               # the generation rules' buffers: made by the first ruled step (see ``_rules_buffers``)
+        self.stopped_at = None                            # run(rules=...): the step that picked a stop token, or None
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
-    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None):
+    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None, rules=None):
         """ONE walk serves every model and every setting: the embedding fetch; per layer an attention half (norm -> wq | wk | wv ->
         rope + cache + attention -> wo -> residual) and an FFN half (norm -> w1 | w3 -> silu -> w2 -> residual, or with an ffnGate the
         routed form: gate + top-2 -> both experts' w1 | w3 as one group of four -> both w2 as one group of two -> mix); then the closing
@@ -299,12 +302,22 @@ class Decoder:
 
         ``sampling``: None -- the step ends in the greedy pick (effort_argmax); a ``Sampling`` -- its settings are written to
         ``self.sample_params`` and the step ends in effort_sample; True -- effort_sample on what ``self.sample_params`` holds (how the
-        step is captured: the graph reads the settings from that tensor at every replay)."""
+        step is captured: the graph reads the settings from that tensor at every replay).
+
+        ``rules``: None -- the pick reads ``self.logits``; a ``Rules`` -- its settings are written to the device (``set_rules``) and the
+        step makes exactly one more call, effort_logit_rules after the LM head: it records the token this step consumed in ``self.seq``,
+        reads ``self.logits`` and writes ``self.logits_ruled``, which the pick (untouched) then reads; ``self.logits`` stays raw.  True
+        -- the same on what the device tensors hold (the captured form)."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         g._bind_stream()
         sampled = sampling is not None and sampling is not False
         if isinstance(sampling, Sampling):
             self.set_sampling(sampling)
+        ruled = rules is not None and rules is not False
+        if isinstance(rules, Rules):
+            self.set_rules(rules)
+        elif ruled:
+            self._rules_buffers()
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
         fn, fg, fr = (part in self.fuse and not dense for part in ("norm", "gate", "resid"))
         bucketed = lambda *ews: not dense and all(ew.bucketsLoaded for ew in ews)   # noqa: E731
@@ -402,16 +415,42 @@ class Decoder:
                 add_product(L.w2, *gated(self.x1, self.x3, self.x2, L.w2), self.ffnOut)                  # :181-183
         rmsnorm(m.norm, self.outNormed)
         basicMul(self.outNormed, m.output, self.logits)                                                  # :222 (sharded: replicated, every rank picks the same token)
-        self._pick(sampled)
+        if ruled:                                          # (sharded: after the replicated LM head, on every rank alike)
+            ck(lib.effort_logit_rules(g.ctx, _p(self.logits), cfg.vocab, _p(self.rules_params), _p(self.tokId), _p(self.pos), _p(self.seq),
+                                      int(self.seq.numel()), _p(self.bias_ids), _p(self.bias_vals), _p(self.stop_pos), _p(self.logits_ruled)), "logit_rules")
+        self._pick(sampled, self.logits_ruled if ruled else self.logits)
 
-    def _pick(self, sampled: bool):
-        """The closing call of every token step: the next token from ``self.logits``, written to tokId and history[pos]; pos += 1."""
+    def _pick(self, sampled: bool, logits=None):
+        """The closing call of every token step: the next token from ``logits`` (``self.logits``, or ``self.logits_ruled`` behind the
+        generation rules), written to tokId and history[pos]; pos += 1."""
         g, lib, n, hl = self.g, _lib.lib(), self.cfg.vocab, int(self.history.numel())
+        logits = self.logits if logits is None else logits
         if not sampled:
-            g.check(lib.effort_argmax(g.ctx, _p(self.logits), n, _p(self.tokId), _p(self.pos), _p(self.history), hl), "argmax")
+            g.check(lib.effort_argmax(g.ctx, _p(logits), n, _p(self.tokId), _p(self.pos), _p(self.history), hl), "argmax")
         else:
-            g.check(lib.effort_sample(g.ctx, _p(self.logits), n, _p(self.sample_params), _p(self.tokId), _p(self.pos), _p(self.history), hl,
+            g.check(lib.effort_sample(g.ctx, _p(logits), n, _p(self.sample_params), _p(self.tokId), _p(self.pos), _p(self.history), hl,
                                       None, None), "sample")
+
+    def _rules_buffers(self):
+        """What effort_logit_rules reads and writes, made on first use: a Decoder that never asks for rules holds none.  ``seq`` (the
+        token every step consumed, int32 [maxTokens]), ``logits_ruled``, ``rules_params`` (effort_rules_params, 64 bytes), the two
+        256-entry bias tables and ``stop_pos`` (-1, i.e. 0xFFFFFFFF, while no stop token has been consumed)."""
+        if self._rules:
+            return
+        dev = self.model.norm.device
+        self.seq = torch.zeros(self.maxTokens, dtype=torch.int32, device=dev)
+        self.logits_ruled = torch.zeros(self.cfg.vocab, dtype=torch.float32, device=dev)
+        self.rules_params, self.bias_ids, self.bias_vals = Rules().to_device(device=dev)
+        self.stop_pos = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        self._rules = True
+
+    def set_rules(self, rules: "Rules", first_pos: int = 0):
+        """Rewrite the device-resident settings of the generation rules and forget an earlier stop (no graph is touched: the captured step
+        reads these tensors).  ``first_pos``: positions below it never stop -- the prompt's."""
+        self.g._bind_stream()
+        self._rules_buffers()
+        rules.to_device(first_pos, self.rules_params, self.bias_ids, self.bias_vals)
+        self.stop_pos.fill_(-1)
 
     def set_sampling(self, sampling: "Sampling"):
         """Rewrite the device-resident settings of the sampled pick (no graph is touched: the captured step reads this tensor)."""
@@ -686,18 +725,20 @@ class Decoder:
                 delta = self.pf_ffnOut
         self.pos.fill_(pos0 + T)
 
-    def _graph(self, effort: float, dense: bool, sampled: bool = False):
+    def _graph(self, effort: float, dense: bool, sampled: bool = False, ruled: bool = False):
         key = ("dense",) if dense else (float(effort),)
         if sampled:                                              # the ONLY thing sampling adds to the key: its settings are device values
             key += ("sampled",)
-        pick = True if sampled else None
+        if ruled:                                                # and the ONLY thing the rules add: one more graph, shared by every Rules
+            key += ("rules",)
+        pick, rules = True if sampled else None, True if ruled else None
         if key not in self._graphs:
             self.reset()
-            self.token_step(effort, dense, pick)                 # warm (handles, kernel attributes, rocBLAS)
+            self.token_step(effort, dense, pick, rules)          # warm (handles, kernel attributes, rocBLAS, the rules' buffers)
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                self.token_step(effort, dense, pick)
+                self.token_step(effort, dense, pick, rules)
             self.g._bind_stream()
             self._graphs[key] = gr
         return self._graphs[key]
@@ -714,10 +755,13 @@ class Decoder:
         self.pos.zero_()
         self.tokId.zero_()
         self.history.zero_()
+        if self._rules:
+            self.seq.zero_()
+            self.stop_pos.fill_(-1)                              # 0xFFFFFFFF: no stop token consumed
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
             collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64,
-            prefill_attention: str = "rows", prefill_ffn: str = "dense", prefill_weights: str = "cores"):
+            prefill_attention: str = "rows", prefill_ffn: str = "dense", prefill_weights: str = "cores", rules=None, stop_poll: int = 16):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
@@ -731,15 +775,31 @@ class Decoder:
         ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
         FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
         and the caches then hold effort-1.0 K / V, not dense ones).
+        ``rules``: a ``Rules`` -- every step applies the generation rules on the device (effort_logit_rules between the LM head and the
+        pick: penalties over the last ``last_n`` tokens fed, the logit bias, min-p), the step graph is shared by every setting, and
+        ``collect_logits`` still returns the RAW logits.  The prompt never stops a run (``first_pos = len(tokenIds)``); prefilled prompt ids
+        are copied into ``seq``, since the kernel records only the steps it runs.  With ``stop_ids``, every ``stop_poll`` replays the
+        4-byte ``stop_pos`` is read back and the loop ends once it is set; the generated picks are then scanned on the host (a stop token
+        picked by the very last step counts), the returned picks end with the stop token, ``stopped_at`` is the step that picked it (else
+        None), and ``pos`` / ``tokId`` are set to continue behind it -- what the replays past it wrote is junk that the next steps
+        overwrite.  With ``forced`` the window is the forced inputs and nothing stops.
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
         if prefill and forced:
             raise ValueError("Decoder.run: prefill=True computes no logits for the prompt, forced=True wants them at every step")
-        gr = self._graph(effort, dense, sampling is not None)
+        if rules is not None and not isinstance(rules, Rules):
+            raise ValueError("Decoder.run: rules is a Rules or None")
+        if int(stop_poll) < 1:
+            raise ValueError("Decoder.run: stop_poll >= 1")
+        gr = self._graph(effort, dense, sampling is not None, *((True,) if rules is not None else ()))    # (a run without rules: today's call)
         self.reset()
         if sampling is not None:
             self.set_sampling(sampling)
+        stops = set(int(t) for t in rules.stop_ids) if rules is not None and not forced else set()
+        self.stopped_at = None
+        if rules is not None:
+            self.set_rules(rules, 0xFFFFFFFF if forced else len(tokenIds))
         logits = []
         t0, timed = None, 0
         skip = min(len(tokenIds) - 1, numTokens) if prefill else 0
@@ -749,6 +809,9 @@ class Decoder:
             self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn, prefill_weights)
             torch.cuda.synchronize()
             self.last_prefill_s = time.perf_counter() - tp
+            if rules is not None:
+                self.seq[:skip].copy_(torch.tensor([int(t) for t in tokenIds[:skip]], dtype=torch.int32))
+        ran = skip                                               # steps 0 .. ran - 1 have a cache row (and, from ``skip`` on, a pick)
         for step in range(skip, numTokens):
             if step < len(tokenIds):
                 self.tokId.fill_(int(tokenIds[step]))            # prompt (or forced) token; otherwise the previous pick stays
@@ -762,11 +825,20 @@ class Decoder:
                 logits.append(self.logits.clone())
             if step >= 2:
                 timed += 1
+            ran = step + 1
+            if stops and (ran - skip) % int(stop_poll) == 0 and int(self.stop_pos.item()) != -1:
+                break                                            # a stop token was consumed: at most stop_poll replays behind the one that picked it
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / timed if t0 is not None and timed else float("nan")
-        steps = min(numTokens, len(tokenIds)) if forced else numTokens
-        picked = self.history[:steps].cpu().tolist()
+        picked = self.history[:ran].cpu().tolist()
         picked[:skip] = [-1] * skip                              # prefilled positions: nothing was picked there
+        first_generated = len(tokenIds) - 1                      # the pick of the last prompt token's step
+        hit = next((k for k in range(first_generated, ran) if picked[k] in stops), None) if stops else None
+        if hit is not None:
+            self.stopped_at = hit
+            picked, logits = picked[:hit + 1], logits[:hit + 1 - skip]
+            self.pos.fill_(hit + 1)
+            self.tokId.fill_(picked[hit])
         st = self.status()
         if st:
             raise RuntimeError(f"decode loop: device status {st} (1: a step past maxTokens / the history buffer, 2: NaN logits)")

@@ -533,6 +533,56 @@ EFFORT_API int effort_topk(effort_ctx* ctx, const float* logits_dev, int n, int 
 /* Host only -- no context, no HIP call: x0 of the draw at (seed, stream, pos), from the same definition the kernel compiles. */
 EFFORT_API uint32_t effort_sample_bits(uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, uint32_t pos);
 
+/* ---- generation rules: penalties, bias, min-p, stop tokens on the device ------------------------ */
+
+/* The settings of effort_logit_rules live in DEVICE memory, for effort_sample_params' reason: one captured graph serves every
+ * setting.  64 bytes, little endian, no padding.  The host cannot validate device values, so the kernel sanitises them (step 0). */
+#define EFFORT_RULES_MAX_WINDOW 1024
+#define EFFORT_RULES_MAX_BIAS   256
+#define EFFORT_RULES_MAX_STOP   8
+typedef struct effort_rules_params {
+    float    repetition_penalty;       /* 1 = off */
+    float    presence_penalty;         /* 0 = off */
+    float    frequency_penalty;        /* 0 = off */
+    float    min_p_log;                /* f32(ln(min_p)) computed by the HOST; -inf = off */
+    uint32_t last_n;                   /* window length, 0 = no penalties */
+    uint32_t n_bias;
+    uint32_t n_stop;
+    uint32_t first_pos;                /* positions below it never stop (the prompt) */
+    uint32_t stop_ids[EFFORT_RULES_MAX_STOP];
+} effort_rules_params;
+
+/* One launch of one workgroup between the LM head and the pick (effort_argmax / effort_sample) of a token step: logits_out_dev
+ * receives the n logits of logits_in_dev with the rules applied.  Every arithmetic step is ONE float32 operation rounded on its own
+ * (no fused multiply-add, a correctly rounded divide).  pos = *pos_dev is read and never advanced (the pick advances it);
+ * tok = *tok_dev is the token this step consumed.
+ *  0. Sanitise.  repetition_penalty not finite or <= 0 counts as 1; presence_penalty / frequency_penalty not finite as 0; last_n,
+ *     n_bias, n_stop are clamped to the three maxima; min_p_log is active only when finite and <= 0; a bias entry whose value is NaN
+ *     is absent; token ids >= n are ignored, in the window and in the bias table alike.
+ *  1. Record.  If tok_dev and seq_dev are given: pos < seqLen: seq[pos] = tok.  Otherwise nothing is written, the window is empty
+ *     and bit 0 of the context's decode status is raised (the meaning it has for the cache and the history).  Without them the
+ *     window is empty.
+ *  2. Stop.  If stop_pos_dev is given, pos >= first_pos, tok is among stop_ids[0 .. n_stop) and *stop_pos_dev == 0xFFFFFFFF:
+ *     *stop_pos_dev = pos (the stop token was picked at step pos - 1; only the first stop is recorded; no status bit).
+ *  3. Copy.  out = in.  logits_out_dev == logits_in_dev is allowed and gives the same bits.
+ *  4. Penalties.  W = min(last_n, pos + 1), the window is seq[pos + 1 - W .. pos], c the number of times token t occurs in it.
+ *     Each distinct t of the window once: l = out[t]; if repetition_penalty != 1: l = l > 0 ? l / repetition_penalty
+ *     : l * repetition_penalty (the rule of HF RepetitionPenaltyLogitsProcessor and of llama.cpp); l = l - (f32(c) *
+ *     frequency_penalty + presence_penalty), two rounded operations and then the subtraction.
+ *  5. Bias.  out[id] = out[id] + val; for an id named more than once the (present) entry with the highest index is the one
+ *     applied; val = -inf bans a token.
+ *  6. Min-p.  m = the largest non-NaN element of out.  If the rule is active and m is finite: thr = m + min_p_log, every
+ *     element < thr becomes -inf; NaN elements stay.  It acts on the ruled logits at temperature 1: effort_sample's temperature,
+ *     top-k and top-p come after it, on out.
+ * NaN: a NaN logit passes steps 4 and 5 with its bits unchanged, and a NaN that their arithmetic makes of other values (inf - inf) is
+ * stored as 0x7FC00000.  With every rule off, out is in bit for bit, NaN payloads and -0.0 included.
+ * Refusals (EFFORT_ERR_ARG, nothing enqueued): n < 1 or seqLen < 0; then a NULL among logits_in_dev, logits_out_dev, params_dev,
+ * pos_dev; exactly one of tok_dev / seq_dev or of bias_ids_dev / bias_vals_dev.  Without the bias tables n_bias counts as 0;
+ * stop_pos_dev may be NULL, and stop reporting needs tok_dev. */
+EFFORT_API int effort_logit_rules(effort_ctx* ctx, const float* logits_in_dev, int n, const effort_rules_params* params_dev,
+                                  const uint32_t* tok_dev, const uint32_t* pos_dev, uint32_t* seq_dev, int seqLen,
+                                  const uint32_t* bias_ids_dev, const float* bias_vals_dev, uint32_t* stop_pos_dev, float* logits_out_dev);
+
 /* ---- weight layout converter ------------------------------------------------------------------- */
 
 /* func bucketize(_:outTensorsPref:tensors:goQ8:false) -- convert.swift:209-260 with kernels getProbes,

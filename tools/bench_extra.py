@@ -15,7 +15,9 @@ both attention paths; its record also goes to profiles/r10_prefill_attention.jso
 token loop; its record also goes to profiles/r11_prefill_mixtral.json; standalone too) and `prefill_buckets` (prefill straight from the
 bucketed weights beside the core kernel in the same run; its record also goes to profiles/r12_prefill_buckets.json; standalone too) and
 `prefill_q4` (prefill straight from the Q4 buckets beside the core and the FP16 bucket kernel in the same run, and whose K caches a Q4
-decode agrees with; its record also goes to profiles/r13_prefill_q4.json; standalone too).
+decode agrees with; its record also goes to profiles/r13_prefill_q4.json; standalone too) and `decode_rules` (the decode loop with
+the generation rules -- penalties, bias, min-p, stop ids: effort_logit_rules -- beside plain greedy decode, and rules_kernel alone beside
+argmax_kernel and sample_kernel; its record also goes to profiles/r14_decode_rules.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -33,8 +35,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -322,6 +324,36 @@ def decode_mixtral(b, res):
     del plain, folded, model
 
 
+CLOSING_KERNEL_PROTOCOL = ("device events around replays of a captured graph, best of 3 windows; one launch per graph x 512 replays "
+                           "(graph-launch overhead included, the same for both kernels), and 64 launches per graph x 32 replays")
+
+
+def us_per_graph_launch(torch, g, fn, per_graph, replays):
+    """us per launch of ``fn`` (one launch on the context ``g``), captured ``per_graph`` times into one graph: device events around
+    ``replays`` replays, best of 3 windows."""
+    g._bind_stream()
+    fn()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    B._GRAPHS_FOR_LIFE.append(gr)
+    with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+        for _ in range(per_graph):
+            fn()
+    g._bind_stream()
+    for _ in range(20):
+        gr.replay()
+    best = float("inf")
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(replays):
+            gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1) * 1e3 / (replays * per_graph))
+    return round(best, 2)
+
+
 def decode_sampled(b, res):
     """Sampled decode beside greedy decode in ONE process (the yardstick is this process's own greedy figure): Mistral-7B shapes, 25 %
     effort, 64 tokens -- greedy, sampled (top_k 40, temperature 0.8), sampled (top_k 64, top_p 0.9), greedy again -- and the closing
@@ -372,30 +404,8 @@ def decode_sampled(b, res):
         g._bind_stream()
         g.check(lib.effort_sample(g.ctx, p(dec.logits), n, p(dec.sample_params), p(tok), p(pos), None, 0, None, None), "sample")
 
-    def us_per_launch(fn, per_graph, replays):
-        g._bind_stream()
-        fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        B._GRAPHS_FOR_LIFE.append(gr)
-        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-            for _ in range(per_graph):
-                fn()
-        g._bind_stream()
-        for _ in range(20):
-            gr.replay()
-        best = float("inf")
-        for _ in range(3):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(replays):
-                gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) * 1e3 / (replays * per_graph))
-        return round(best, 2)
-    k = {"n": n, "protocol": "device events around replays of a captured graph, best of 3 windows; one launch per graph x 512 replays "
-                            "(graph-launch overhead included, the same for both kernels), and 64 launches per graph x 32 replays"}
+    us_per_launch = lambda fn, per_graph, replays: us_per_graph_launch(torch, g, fn, per_graph, replays)      # noqa: E731
+    k = {"n": n, "protocol": CLOSING_KERNEL_PROTOCOL}
     for name, sm in (("sample_top_k_40_temperature_0.8", Sampling(temperature=0.8, top_k=40, seed=1)),
                      ("sample_top_k_64_top_p_0.9", Sampling(temperature=1.0, top_k=64, top_p=0.9, seed=1))):
         dec.set_sampling(sm)
@@ -405,6 +415,92 @@ def decode_sampled(b, res):
     res["decode_sampled"] = out
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "r08_decode_sampled.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
+def decode_rules(b, res):
+    """Decode with the generation rules (effort_logit_rules between the LM head and the pick) beside plain greedy decode in ONE process,
+    decode_sampled's protocol: Mistral-7B shapes, 25 % effort, 64 tokens -- greedy, Rules(repetition_penalty=1.1) at last_n 64, a full
+    load (last_n 1024, 256 biases, min_p 0.05, one stop id that never occurs), greedy again -- and rules_kernel alone at n = 32000 under
+    the same three settings, argmax_kernel and sample_kernel beside it in the same run."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    from effort_amd.rules import Rules
+    from effort_amd.sampling import Sampling
+    torch = b.torch
+    b.g.set_tuning(0, 0, 0)
+    torch.cuda.empty_cache()
+    prompt, nt = [1, 733, 16289, 28793, 22557], 64
+    model = Model.random(MistralConfig(), seed=1)
+    n = model.cfg.vocab
+    dec = Decoder(model, maxTokens=nt + 8)
+    B._GRAPHS_FOR_LIFE.append(dec._graphs)
+    light = Rules(repetition_penalty=1.1, last_n=64)
+    full = Rules(repetition_penalty=1.1, presence_penalty=0.1, frequency_penalty=0.1, last_n=1024, min_p=0.05,
+                 logit_bias={1000 + 97 * i: (-1.0 if i % 2 else 0.5) for i in range(256)}, stop_ids=(n - 1,))
+
+    def tps(**kw):
+        best, ids = 0.0, None
+        for _ in range(3):
+            ids, dt, _ = dec.run(prompt, nt, effort=0.25, **kw)
+            best = max(best, 1 / dt)
+        return round(best, 1), ids
+    out = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "tokens": nt, "effort": 0.25,
+           "protocol": "best of 3 runs of 64 tokens, hipGraph replay, timed from the 3rd step; the four figures in this order, one process; "
+                       "the full load polls stop_pos every 16 replays (4 bytes, one synchronisation)",
+           "full_load": "last_n 1024 (the window of a 64-token run holds at most 64 ids), 256 biases, min_p 0.05, penalties 1.1 / 0.1 / 0.1, one stop id never picked"}
+    out["greedy_tokens_per_s"], ids_g = tps()
+    out["rules_repetition_1.1_last_n_64_tokens_per_s"], ids_a = tps(rules=light)
+    out["rules_full_load_tokens_per_s"], ids_b = tps(rules=full)
+    out["greedy_again_tokens_per_s"], ids_g2 = tps()
+    greedy = (out["greedy_tokens_per_s"] + out["greedy_again_tokens_per_s"]) / 2
+    out["greedy_run_to_run"] = round(out["greedy_again_tokens_per_s"] / out["greedy_tokens_per_s"] - 1, 4)
+    out["rules_repetition_vs_greedy_mean"] = round(out["rules_repetition_1.1_last_n_64_tokens_per_s"] / greedy - 1, 4)
+    out["rules_full_load_vs_greedy_mean"] = round(out["rules_full_load_tokens_per_s"] / greedy - 1, 4)
+    out["greedy_runs_agree"] = ids_g == ids_g2
+    out["ruled_runs_leave_the_greedy_text"] = [ids_a != ids_g, ids_b != ids_g]
+    out["full_load_stopped_at"] = dec.stopped_at
+    # the kernels alone, on the last step's logits; the window of the rules is FULL there: a seq of its own, 1024 + 8 ids out of a pool
+    # of 300, the position at 1024 + 4
+    g, lib = dec.g, effort_amd.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    tok, pos = torch.zeros(1, dtype=torch.int32, device=b.dev), torch.zeros(1, dtype=torch.int32, device=b.dev)
+    rpos = torch.full((1,), 1024 + 4, dtype=torch.int32, device=b.dev)           # (effort_logit_rules reads the position and never advances it)
+    seq = (torch.arange(1024 + 8, dtype=torch.int64) * 7919 % 300 * 101 % n).to(torch.int32).to(b.dev)
+
+    def launch_argmax():
+        g._bind_stream()                                                         # (inside a capture: the capture's stream)
+        g.check(lib.effort_argmax(g.ctx, p(dec.logits), n, p(tok), p(pos), None, 0), "argmax")
+
+    def launch_sample():
+        g._bind_stream()
+        g.check(lib.effort_sample(g.ctx, p(dec.logits), n, p(dec.sample_params), p(tok), p(pos), None, 0, None, None), "sample")
+
+    def launch_rules():
+        g._bind_stream()
+        g.check(lib.effort_logit_rules(g.ctx, p(dec.logits), n, p(dec.rules_params), p(tok), p(rpos), p(seq), int(seq.numel()), p(dec.bias_ids),
+                                       p(dec.bias_vals), p(dec.stop_pos), p(dec.logits_ruled)), "logit_rules")
+    us = lambda fn: {"us_per_launch_one_per_graph": us_per_graph_launch(torch, g, fn, 1, 512),       # noqa: E731
+                     "us_per_launch_64_per_graph": us_per_graph_launch(torch, g, fn, 64, 32)}
+    k = {"n": n, "protocol": CLOSING_KERNEL_PROTOCOL, "rules_position": 1024 + 4}
+    k["argmax"] = us(launch_argmax)
+    dec.set_sampling(Sampling(temperature=0.8, top_k=40, seed=1))
+    k["sample_top_k_40_temperature_0.8"] = us(launch_sample)
+    for name, r in (("rules_off", Rules()), ("rules_repetition_1.1_last_n_64", light),
+                    ("rules_window_1024_only", Rules(repetition_penalty=1.1, presence_penalty=0.1, frequency_penalty=0.1, last_n=1024)),
+                    ("rules_256_biases_only", Rules(last_n=0, logit_bias=full.logit_bias)), ("rules_min_p_only", Rules(last_n=0, min_p=0.05)),
+                    ("rules_full_load", full)):
+        dec.set_rules(r, 5)
+        k[name] = us(launch_rules)
+    k["argmax_again"] = us(launch_argmax)
+    out["kernel_alone"] = k
+    res["decode_rules"] = out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r14_decode_rules.json"), "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
     del dec, model
@@ -921,7 +1017,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
-       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4}
+       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules}
 
 
 class Light:

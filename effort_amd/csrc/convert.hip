@@ -5,7 +5,7 @@
 //
 // MI355X design: one 1024-thread workgroup per INPUT row keeps the whole row (values + u16 indices,
 // zero-padded to the next power of two exactly as sortAbs pads) in LDS -- up to 16384 x 4 B = 64 KiB of
-// the CU's 160 KiB -- and runs the reference's compare-exchange network there, stage by stage with one
+// the CU's 160 KiB, 130 KiB with the bucket scratch and the rank rows: 16384 outputs is the largest row -- and runs the reference's compare-exchange network there, stage by stage with one
 // barrier each, so ties in |w| land exactly where the reference's network puts them.  The rank of an
 // element inside its bucket (= how many members of the same 16-output bucket precede it in the sorted
 // order, what preBucketize's running counters compute) is found in parallel from the inverse
@@ -159,14 +159,16 @@ __global__ __launch_bounds__(256) void make_stats_kernel(const uint16_t* __restr
 
 hipError_t launch_convert_fp16(const uint16_t* W, uint32_t outDim, uint32_t inDim, uint16_t* buckets, uint32_t pitchCols,
                                uint16_t* stats, uint16_t* probes, uint16_t* scratchVals, int* status, hipStream_t st) {
-    const uint32_t rep = outDim >= (uint32_t)kProbes ? 1u : (uint32_t)kProbes / outDim;
-    hipLaunchKernelGGL(probes_kernel, dim3((kProbes / rep + 255) / 256), dim3(256), 0, st, W, probes, inDim, rep);
-    hipLaunchKernelGGL(transpose_kernel, dim3((inDim + 63) / 64, (outDim + 63) / 64), dim3(256), 0, st, W, scratchVals, outDim, inDim);
     // sortAbs padding: exact powers of two are sorted in place, everything else in 2^(floor(log2 n)+1)
     uint32_t P = 1; while (P < outDim) P <<= 1;
     const uint32_t C = outDim / kB;
+    // 16384 outputs take 133136 bytes; the next size, 16448, pads to 32768 and would take 198936 (refused before anything is enqueued;
+    // the entry point refuses outDim > 16384 ahead of this: tests/test_gpu_converter_edges.py::test_size_limit)
     const uint32_t lds = P * 4 + C * (kB + 1) * 2 + outDim * 2 + 16;
     if (lds > 160u * 1024u - 64u) return hipErrorInvalidValue;
+    const uint32_t rep = outDim >= (uint32_t)kProbes ? 1u : (uint32_t)kProbes / outDim;
+    hipLaunchKernelGGL(probes_kernel, dim3((kProbes / rep + 255) / 256), dim3(256), 0, st, W, probes, inDim, rep);
+    hipLaunchKernelGGL(transpose_kernel, dim3((inDim + 63) / 64, (outDim + 63) / 64), dim3(256), 0, st, W, scratchVals, outDim, inDim);
     {
         hipError_t e = allow_full_lds(reinterpret_cast<const void*>(&sort_bucketize_kernel));
         if (e != hipSuccess) return e;

@@ -275,6 +275,10 @@ hipError_t launch_mix2_add_rows(float* h, const float* f, const float* val, uint
 hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
                                   uint32_t numHeads, uint32_t headDim, hipStream_t st);
 
+// decode attention with the keys split across workgroups and one cache copy read per KV group (attention_split.hip): two launches
+hipError_t launch_attention_split(const float* q, const float* kCache, const float* vCache, const uint32_t* pos, float* out, float* scratch,
+                                  uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t maxTokens, uint32_t splits, hipStream_t st);
+
 // the sampled pick (sample.hip)
 hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
                          int* status, uint32_t* topkIdx, float* topkVal, hipStream_t st);

@@ -2,6 +2,7 @@
 // rocblas.h), both converters, cosine, the decode-loop glue, the prompt-prefill block calls, sampling and the two status words.
 #include <rocblas/rocblas.h>
 
+#include "attention_split.h"
 #include "host.h"
 #include "prefill.h"
 #include "sample_device.h"
@@ -125,6 +126,33 @@ extern "C" int effort_rope_attention(effort_ctx* c, const float* xq, const float
         (headDim != 64 && headDim != 128 && headDim != 256))
         return fail(c, EFFORT_ERR_SHAPE, "rope_attention: headDim 64/128/256, maxTokens <= 8192");
     return HIP_RC(c, launch_rope_attention(xq, xk, xv, kCache, vCache, pos, out, numHeads, numHeadsKV, headDim, maxTokens, ropeBase, c->d_status + 1, c->stream));
+}
+// ---- the split decode attention (attention_split.hip): two launches, nothing allocated -- legal inside a stream capture
+extern "C" int64_t effort_attention_split_scratch_bytes(int numHeads, int headDim, int splits) {
+    if (numHeads <= 0 || (headDim != 64 && headDim != 128 && headDim != 256) || splits < 1 || splits > (int)kSplitMax) return 0;
+    return (int64_t)(attention_split_scratch_floats((uint32_t)numHeads, (uint32_t)headDim, (uint32_t)splits) * sizeof(float));
+}
+extern "C" int effort_attention_split_default_splits(effort_ctx* c, int numHeadsKV, int maxTokens) {
+    if (!c || numHeadsKV <= 0 || maxTokens <= 0) return EFFORT_ERR_ARG;
+    return attention_split_default(c->env.numCU, numHeadsKV, maxTokens);
+}
+extern "C" int effort_attention_split(effort_ctx* c, const float* q, const float* kCache, const float* vCache, const uint32_t* pos, float* out,
+                                      float* scratch, int numHeads, int numHeadsKV, int headDim, int maxTokens, int splits) {
+    if (!c || !q || !kCache || !vCache || !pos || !out || !scratch) return fail(c, EFFORT_ERR_ARG, "attention_split: null argument");
+    JOIN_TRY(c);
+    if (maxTokens <= 0 || maxTokens > 8192 || !attention_split_shape_ok(numHeads, numHeadsKV, headDim))
+        return fail(c, EFFORT_ERR_SHAPE, "attention_split: headDim 64/128/256, numHeads / numHeadsKV 1/2/4/8, maxTokens <= 8192");
+    if (splits < 0 || splits > (int)kSplitMax) return fail(c, EFFORT_ERR_ARG, "attention_split: 0 <= splits <= 64");
+    const int S = splits ? splits : attention_split_default(c->env.numCU, numHeadsKV, maxTokens);
+    return HIP_RC(c, launch_attention_split(q, kCache, vCache, pos, out, scratch, (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim,
+                                            (uint32_t)maxTokens, (uint32_t)S, c->stream));
+}
+extern "C" int effort_debug_attention_split_range(int nTok, int splits, int split, int* tiles2) {
+    if (nTok < 1 || splits < 1 || splits > (int)kSplitMax || split < 0 || split >= splits || !tiles2) return EFFORT_ERR_ARG;
+    uint32_t t0, t1;
+    attention_split_tiles((uint32_t)nTok, (uint32_t)splits, (uint32_t)split, t0, t1);
+    tiles2[0] = (int)t0; tiles2[1] = (int)t1;
+    return EFFORT_OK;
 }
 extern "C" int effort_silu_mul(effort_ctx* c, const float* x1, const float* x3, float* out, int n) {
     if (!c || !x1 || !x3 || !out || n <= 0) return fail(c, EFFORT_ERR_ARG, "silu_mul: bad argument");

@@ -185,10 +185,17 @@ class Decoder:
     ``fused_attention``: True -- rope, the cache write and the attention of a layer are one launch (effort_rope_attention).  False
     -- two (effort_rope_kv + effort_attention), but ONLY in the steps that fold no glue on an FP16 model, and in every ``dense=True``
     step: a step with any of norm / gate / resid folded, a column-sharded step and every effort step of a model with Q4 or core-only
-    bundles keep the one launch whatever this says."""
+    bundles keep the one launch whatever this says.
+
+    ``split_attention_from``: None -- the attention above at every position.  An integer P -- ``run`` takes every step at a position
+    >= P through a second captured step (``token_step(split=True)``) whose attention is effort_rope_kv + effort_attention_split: the
+    keys split across workgroups, one cache copy read per KV group (csrc/attention_split.hip), for every model kind and setting the
+    step serves, dense included.  Same caches, same layout; logits within the f32 bar of the other step's, not its bits.  Needs
+    numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256 and maxTokens <= 8192; not with a column-sharded decoder."""
 
     def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
-                 world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False):
+                 world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False,
+                 split_attention_from: int | None = None):
         cfg = self.cfg = model.cfg
         # A model with Q4 or core-only bundles (Model.random(q4=True) / Model.load(q4=True)).  token_step dispatches every multiply per
         # BUNDLE; an all-FP16 model is the case in which every bundle is a bucketed FP16 one.
@@ -269,6 +276,18 @@ class Decoder:
         self.history = torch.zeros(self.maxTokens, dtype=torch.int32, device=dev)
         self.sample_params = Sampling().to_device(device=dev)     # effort_sample_params, 32 bytes: the sampled pick reads its settings HERE
         self._graphs: dict = {}
+        self.split_attention_from = None if split_attention_from is None else int(split_attention_from)
+        self.splitScratch = None                          # effort_attention_split's partial states: one buffer, shared by the layers
+        if self.split_attention_from is not None:
+            if self.sharded:
+                raise ValueError("Decoder: split_attention_from is not implemented for the column-sharded decode loop")
+            lib = _lib.lib()
+            splits = lib.effort_attention_split_default_splits(self.g.ctx, cfg.numHeadsKV, self.maxTokens)
+            nbytes = lib.effort_attention_split_scratch_bytes(cfg.numHeads, cfg.headDim, max(splits, 1))
+            if (self.split_attention_from < 0 or splits < 1 or nbytes <= 0 or self.maxTokens > 8192 or cfg.numHeads % cfg.numHeadsKV
+                    or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8)):
+                raise ValueError("Decoder: split_attention_from >= 0 needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 8192")
+            self.splitScratch = f(nbytes // 4)
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
         self._pf = None                                   # prefill's block buffers: made by the first ``prefill`` (see ``_prefill_buffers``)
         self.last_prefill_s = None                        # run(prefill=True): synchronised wall time of its prefill
@@ -276,7 +295,7 @@ class Decoder:
         self.stopped_at = None                            # run(rules=...): the step that picked a stop token, or None
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
-    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None, rules=None):
+    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None, rules=None, split: bool = False):
         """ONE walk serves every model and every setting: the embedding fetch; per layer an attention half (norm -> wq | wk | wv ->
         rope + cache + attention -> wo -> residual) and an FFN half (norm -> w1 | w3 -> silu -> w2 -> residual, or with an ffnGate the
         routed form: gate + top-2 -> both experts' w1 | w3 as one group of four -> both w2 as one group of two -> mix); then the closing
@@ -307,8 +326,13 @@ class Decoder:
         ``rules``: None -- the pick reads ``self.logits``; a ``Rules`` -- its settings are written to the device (``set_rules``) and the
         step makes exactly one more call, effort_logit_rules after the LM head: it records the token this step consumed in ``self.seq``,
         reads ``self.logits`` and writes ``self.logits_ruled``, which the pick (untouched) then reads; ``self.logits`` stays raw.  True
-        -- the same on what the device tensors hold (the captured form)."""
+        -- the same on what the device tensors hold (the captured form).
+
+        ``split``: every layer's attention is effort_rope_kv + effort_attention_split (three launches: the cache write, the partial
+        states, their merge) whatever ``fused_attention`` and the folded glue say; a Decoder made with ``split_attention_from``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
+        if split and self.splitScratch is None:
+            raise ValueError("Decoder.token_step(split=True): make the Decoder with split_attention_from")
         g._bind_stream()
         sampled = sampling is not None and sampling is not False
         if isinstance(sampling, Sampling):
@@ -368,11 +392,15 @@ class Decoder:
 
         def attention(n):                                  # xq_temp, xk_temp, xv_temp -> attnOutput, the caches at pos written
             kc, vc, rope = _p(self.kCache[n]), _p(self.vCache[n]), C.c_float(cfg.ropeBase)
-            if self._two_launch_attention[bool(dense)]:
+            if split or self._two_launch_attention[bool(dense)]:
                 ck(lib.effort_rope_kv(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
                                       cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv")
-                ck(lib.effort_attention(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.headDim,
-                                        self.maxTokens), "attention")
+                if split:
+                    ck(lib.effort_attention_split(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), _p(self.splitScratch),
+                                                  cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, 0), "attention_split")
+                else:
+                    ck(lib.effort_attention(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), cfg.numHeads, cfg.headDim,
+                                            self.maxTokens), "attention")
             else:
                 ck(lib.effort_rope_attention(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), kc, vc, _p(self.pos),
                                              _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_attention")
@@ -725,20 +753,23 @@ class Decoder:
                 delta = self.pf_ffnOut
         self.pos.fill_(pos0 + T)
 
-    def _graph(self, effort: float, dense: bool, sampled: bool = False, ruled: bool = False):
+    def _graph(self, effort: float, dense: bool, sampled: bool = False, ruled: bool = False, split: bool = False):
         key = ("dense",) if dense else (float(effort),)
         if sampled:                                              # the ONLY thing sampling adds to the key: its settings are device values
             key += ("sampled",)
         if ruled:                                                # and the ONLY thing the rules add: one more graph, shared by every Rules
             key += ("rules",)
+        if split:                                                # ... and the split attention: the step of the positions >= split_attention_from
+            key += ("split",)
         pick, rules = True if sampled else None, True if ruled else None
+        step = (effort, dense, pick, rules) + ((True,) if split else ())         # (without the option: today's call)
         if key not in self._graphs:
             self.reset()
-            self.token_step(effort, dense, pick, rules)          # warm (handles, kernel attributes, rocBLAS, the rules' buffers)
+            self.token_step(*step)                               # warm (handles, kernel attributes, rocBLAS, the rules' buffers)
             torch.cuda.synchronize()
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                self.token_step(effort, dense, pick, rules)
+                self.token_step(*step)
             self.g._bind_stream()
             self._graphs[key] = gr
         return self._graphs[key]
@@ -783,6 +814,7 @@ class Decoder:
         picked by the very last step counts), the returned picks end with the stop token, ``stopped_at`` is the step that picked it (else
         None), and ``pos`` / ``tokId`` are set to continue behind it -- what the replays past it wrote is junk that the next steps
         overwrite.  With ``forced`` the window is the forced inputs and nothing stops.
+        With ``split_attention_from`` = P the steps at positions >= P replay the split-attention graph, the others the ordinary one.
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
@@ -793,6 +825,8 @@ class Decoder:
         if int(stop_poll) < 1:
             raise ValueError("Decoder.run: stop_poll >= 1")
         gr = self._graph(effort, dense, sampling is not None, *((True,) if rules is not None else ()))    # (a run without rules: today's call)
+        splitFrom = self.split_attention_from                    # (both graphs BEFORE the reset: _graph resets the position)
+        grSplit = None if splitFrom is None else self._graph(effort, dense, sampling is not None, rules is not None, split=True)
         self.reset()
         if sampling is not None:
             self.set_sampling(sampling)
@@ -820,7 +854,7 @@ class Decoder:
             if step == max(2, skip):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-            gr.replay()
+            (gr if grSplit is None or step < splitFrom else grSplit).replay()    # (the host's step counter is the position)
             if collect_logits:
                 logits.append(self.logits.clone())
             if step >= 2:

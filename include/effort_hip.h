@@ -315,6 +315,28 @@ EFFORT_API int effort_attention(effort_ctx* ctx, const float* q_dev, const float
 EFFORT_API int effort_rope_attention(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* k_cache_dev,
                           float* v_cache_dev, const uint32_t* pos_dev, float* out_dev, int numHeads, int numHeadsKV, int headDim,
                           int maxTokens, float ropeBase);
+/* effort_attention_split: effort_attention's result -- out[h] = softmax(q[h] . K[t] / sqrt(headDim)) . V[t] over cache rows 0 .. *pos_dev
+ * (nTok = min(*pos_dev + 1, maxTokens) rows, as effort_attention clamps; the row at *pos_dev was written by effort_rope_kv) -- for long
+ * contexts: the keys are split across `splits` workgroups per KV group and each workgroup serves the numHeads / numHeadsKV query heads of
+ * its group from ONE cache copy.  Two launches on the context's stream (partial online-softmax states into scratch_dev, then their merge);
+ * nothing is allocated, so the call may be captured, and the grid does not depend on the position: a captured call serves every position.
+ *   q_dev f32 [numHeads * headDim] (roped), caches f32 [maxTokens][numHeads][headDim], out_dev f32 [numHeads * headDim];
+ *   scratch_dev: effort_attention_split_scratch_bytes(numHeads, headDim, S) bytes -- 4 * numHeads * S * (headDim + 2), S the resolved number
+ *   of splits; 0 for a shape or an S the call refuses.  It holds no state between calls.
+ *   splits 1 .. 64, or 0: effort_attention_split_default_splits(ctx, numHeadsKV, maxTokens) -- ceil(CUs / numHeadsKV), at most the 64-key
+ *   tiles of maxTokens, at most 64: one to two workgroups per CU, no split thinner than a tile of the full cache.
+ * ONLY the cache copy of head g * (numHeads / numHeadsKV) of KV group g is read: a caller whose copies of a group differ gets the
+ * attention of the first copy for every head of the group.  No cache row past *pos_dev is read.
+ * Bar: every element within 2e-5 * max|out| of the float64 value and cos-sim >= 0.999999 (effort_attention_block's).  The output's bits
+ * are a function of q, cache rows 0 .. *pos_dev, *pos_dev, the resolved splits and numHeads / numHeadsKV; they are identical run to run and
+ * they are NOT the bits of effort_attention / effort_rope_attention (another order of the sums).
+ * Refusals, nothing enqueued, in this order: a null argument (scratch_dev included) EFFORT_ERR_ARG; numHeads / numHeadsKV not 1, 2, 4 or 8,
+ * headDim not 64 / 128 / 256, maxTokens outside 1 .. 8192 EFFORT_ERR_SHAPE; splits outside 0 .. 64 EFFORT_ERR_ARG. */
+EFFORT_API int64_t effort_attention_split_scratch_bytes(int numHeads, int headDim, int splits);
+EFFORT_API int effort_attention_split_default_splits(effort_ctx* ctx, int numHeadsKV, int maxTokens);
+EFFORT_API int effort_attention_split(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev,
+                           const uint32_t* pos_dev, float* out_dev, float* scratch_dev, int numHeads, int numHeadsKV, int headDim,
+                           int maxTokens, int splits);
 /* silu(x1, x3, out:) = x3 * x1 / (1 + exp(-x1)) (matrix.metal:25-35). */
 EFFORT_API int effort_silu_mul(effort_ctx* ctx, const float* x1_dev, const float* x3_dev, float* out_dev, int n);
 /* tokEmbeddings.fetchRow(id, out:) (aux.metal:355): row *id_dev of an f16 [vocab][n] table as f32. */

@@ -17,7 +17,10 @@ bucketed weights beside the core kernel in the same run; its record also goes to
 `prefill_q4` (prefill straight from the Q4 buckets beside the core and the FP16 bucket kernel in the same run, and whose K caches a Q4
 decode agrees with; its record also goes to profiles/r13_prefill_q4.json; standalone too) and `decode_rules` (the decode loop with
 the generation rules -- penalties, bias, min-p, stop ids: effort_logit_rules -- beside plain greedy decode, and rules_kernel alone beside
-argmax_kernel and sample_kernel; its record also goes to profiles/r14_decode_rules.json; standalone too).
+argmax_kernel and sample_kernel; its record also goes to profiles/r14_decode_rules.json; standalone too) and `decode_attention_split`
+(a decode step's attention by position: the one- and two-launch attention beside effort_attention_split on rotating caches, and the
+decode loop from position 4000 and from 0 with and without `split_attention_from`; its record also goes to
+profiles/r15_attention_split.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -35,8 +38,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1001,6 +1004,137 @@ def prefill_attention(b, res):
     del model
 
 
+def alternating_us(b, fns, calls):
+    """us per library call of every leg of ``fns`` ({name: fn}, ``calls`` calls each): us_per_call's protocol -- a warm call, one graph per
+    leg, 3 warm replays, device events around 4 replays per window, best of 3 windows -- with the legs' windows ALTERNATING in one process."""
+    torch, g = b.torch, b.g
+    graphs = {}
+    for name, fn in fns.items():
+        g._bind_stream()
+        fn()
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        B._GRAPHS_FOR_LIFE.append(gr)
+        with torch.cuda.graph(gr, capture_error_mode="thread_local"):
+            fn()
+        g._bind_stream()
+        for _ in range(3):
+            gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    best = {name: float("inf") for name in fns}
+    for _ in range(3):
+        for name, gr in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            best[name] = min(best[name], e0.elapsed_time(e1) * 1e3 / (4 * calls))
+    return best
+
+
+def decode_attention_split(b, res):
+    """Decode attention by position: effort_rope_attention (one launch) and effort_rope_kv + effort_attention (two) beside effort_rope_kv +
+    effort_attention_split (three: the keys split across workgroups, one cache copy per KV group) at the default splits and at 8 and 64,
+    one process, the legs' windows alternating.  Kernel legs, prefill_attention's protocol: 32 heads, 8 KV heads, headDim 128, maxTokens
+    8192, a pass over four ROTATING cache pairs (1 GB) per graph, device events; us per step's attention, the K / V bytes each path asks
+    for and bytes over time.  Model legs, Mistral-7B shapes, 25 % effort: tokens/s over 64 captured steps from position 4000 (after a
+    `prefill(attention="block")` of 4000 tokens) and from position 0, split_attention_from None, 0, None again."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(79)
+    nh, nkv, hd, maxTokens, pairs, rope = 32, 8, 128, 8192, 4, C.c_float(1e6)
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    caches = [(rnd(maxTokens, nh, hd), rnd(maxTokens, nh, hd)) for _ in range(pairs)]
+    xq, xk, xv, qr, out = rnd(nh * hd), rnd(nkv * hd), rnd(nkv * hd), rnd(nh * hd), torch.zeros(nh * hd, device=b.dev)
+    default = lib.effort_attention_split_default_splits(g.ctx, nkv, maxTokens)
+    scratch = torch.zeros(lib.effort_attention_split_scratch_bytes(nh, hd, 64) // 4, device=b.dev)
+    posd = torch.zeros(1, dtype=torch.int32, device=b.dev)
+
+    def leg(kind, S=0):
+        def fn():
+            g._bind_stream()
+            for kc, vc in caches:
+                if kind == "rope_attention":
+                    g.check(lib.effort_rope_attention(g.ctx, p(xq), p(xk), p(xv), p(kc), p(vc), p(posd), p(out), nh, nkv, hd, maxTokens, rope), kind)
+                    continue
+                g.check(lib.effort_rope_kv(g.ctx, p(xq), p(xk), p(xv), p(qr), p(kc), p(vc), p(posd), nh, nkv, hd, maxTokens, rope), "rope_kv")
+                if kind == "rope_kv+attention":
+                    g.check(lib.effort_attention(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), nh, hd, maxTokens), kind)
+                else:
+                    g.check(lib.effort_attention_split(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), p(scratch), nh, nkv, hd, maxTokens, S), kind)
+        return fn
+    legs = {"rope_attention": leg("rope_attention"), "rope_kv+attention": leg("rope_kv+attention"),
+            f"rope_kv+attention_split_default_{default}": leg("split", 0), "rope_kv+attention_split_8": leg("split", 8),
+            "rope_kv+attention_split_64": leg("split", 64)}
+    kern = {"protocol": "a step's attention on each of 4 rotating cache pairs per graph, 4 replays per window, best of 3 windows, device events, the legs' "
+                        "windows alternating; kv_bytes = live rows x the K + V bytes a path asks for per row (32 KB: every head's copy; 8 KB: one "
+                        "copy per KV group) + the partial states written and read",
+            "heads": nh, "headsKV": nkv, "headDim": hd, "maxTokens": maxTokens, "default_splits": default}
+    for pos in (63, 255, 1023, 4095, 8191):
+        posd.fill_(pos)
+        us, row = alternating_us(b, legs, pairs), {}
+        for name, t in us.items():
+            S = default if "default" in name else int(name.rsplit("_", 1)[1]) if "split" in name else 0
+            asked = (pos + 1) * hd * 4 * 2 * (nkv if S else nh) + 2 * nh * S * (hd + 2) * 4
+            row[name] = {"us_per_step": round(t, 2), "kv_bytes": asked, "TBps_of_kv_bytes": round(asked / t / 1e6, 3)}
+        row["rope_attention_over_split_default_time"] = round(us["rope_attention"] / us[f"rope_kv+attention_split_default_{default}"], 3)
+        kern[f"pos_{pos}"] = row
+    del caches
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (4000,), generator=torch.Generator().manual_seed(3))]
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "effort": 0.25, "maxTokens": 4096,
+         "protocol": "both step graphs captured, then Decoder.prefill(attention='block') of 4000 tokens; per leg the position is set, 4 warm replays, the "
+                     "position set again, 64 replays between synchronised wall-clock reads, best of 2; 'None' legs replay the ordinary step of a "
+                     "Decoder made without the option, '0' the split step of one made with split_attention_from=0"}
+    decs = {}
+    for name, split in (("None", None), ("0", 0)):
+        dec = Decoder(model, maxTokens=4096, split_attention_from=split)
+        gr = dec._graph(0.25, False, split=split is not None)
+        B._GRAPHS_FOR_LIFE.extend(dec._graphs.values())
+        dec.prefill(prompt, attention="block")
+        decs[name] = (dec, gr)
+    for start in (4000, 0):
+        for name in ("None", "0", "None"):
+            dec, gr = decs[name]
+            best = float("inf")
+            for _ in range(2):
+                for steps in (4, 64):
+                    dec.pos.fill_(start)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(steps):
+                        gr.replay()
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                best = min(best, dt)
+            key = f"from_{start}_split_attention_from_{name}_tokens_per_s"
+            m[key + "_again" if key in m else key] = round(64 / best, 1)
+        m[f"from_{start}_split_over_none"] = round(m[f"from_{start}_split_attention_from_0_tokens_per_s"] / m[f"from_{start}_split_attention_from_None_tokens_per_s"], 3)
+    m["decode_status"] = [dec.status() for dec, _ in decs.values()]
+    res_out["model"] = m
+    res["decode_attention_split"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r15_attention_split.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del decs, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1017,7 +1151,8 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "heavy_tailed_input": heavy_tailed_input, "sweep_structured": sweep_structured, "other_shapes": other_shapes,
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
-       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules}
+       "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
+       "decode_attention_split": decode_attention_split}
 
 
 class Light:

@@ -43,11 +43,23 @@ namespace effort {
 constexpr int kAbWaves = 4;
 
 typedef float ab_f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 ab_f16x4 __attribute__((ext_vector_type(4)));
 
-template <int HD>
-__global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const float* __restrict__ qAll, const float* __restrict__ kCache,
-                                                                        const float* __restrict__ vCache, uint32_t pos0, uint32_t rows,
-                                                                        float* __restrict__ outAll, uint32_t numHeads) {
+// The cache element T.  float: [maxTokens][numHeads][headDim], kvRep = 1.  _Float16: the compact cache [maxTokens][numHeads / kvRep][headDim]
+// (kv16.hip), head h reading KV head h / kvRep.  A lane's four consecutive elements are ONE load either way -- 16 bytes, or 8 that stay
+// halves in registers until the product that consumes them widens them (exact) -- so the lane maps, the order of the sums and with
+// them the chunk independence below are those of the f32 cache whatever T is.
+template <typename T> struct ab_cache;
+template <> struct ab_cache<float> { typedef ab_f32x4 raw; };
+template <> struct ab_cache<_Float16> { typedef ab_f16x4 raw; };
+__device__ __forceinline__ ab_f32x4 ab_widen(ab_f32x4 x) { return x; }
+__device__ __forceinline__ ab_f32x4 ab_widen(ab_f16x4 x) { return __builtin_convertvector(x, ab_f32x4); }
+
+template <int HD, typename T>
+__global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const float* __restrict__ qAll, const T* __restrict__ kCache,
+                                                                        const T* __restrict__ vCache, uint32_t pos0, uint32_t rows,
+                                                                        float* __restrict__ outAll, uint32_t numHeads, uint32_t kvRep) {
+    typedef typename ab_cache<T>::raw raw4;
     constexpr int NJ = HD / 16;                         // 16-byte pieces of a K (and q) row per lane
     constexpr int NV = HD / 64;                         // 16-byte pieces of a V row per lane and key
     constexpr int kPitch = HD + 4;                      // (a pitch of HD puts the 16 queries on the same banks)
@@ -58,6 +70,7 @@ __global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const fl
     const uint32_t limit = pos0 + rows;                 // no cache row at or past it is read
     const uint32_t r = qt * 16u + c, qpos = pos0 + r;   // this lane's query: row of the block, absolute position
     const size_t rowStride = (size_t)numHeads * HD;
+    const uint32_t cHeads = numHeads / kvRep, cHead = head / kvRep;     // the cache's heads per row, this head's among them
     const uint32_t lastTile = (pos0 + min(qt * 16u + 15u, rows - 1u)) >> 4;
     const float scale = 1.0f / sqrtf((float)HD);
 
@@ -70,17 +83,17 @@ __global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const fl
             q[j] = r < rows ? x : ab_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         }
     }
-    auto ask_k = [&](uint32_t t, ab_f32x4 (&k)[NJ]) {
-        const float* kp = kCache + ((size_t)min(t * 16u + c, limit - 1u) * numHeads + head) * HD + 4u * g;
+    auto ask_k = [&](uint32_t t, raw4 (&k)[NJ]) {
+        const T* kp = kCache + ((size_t)min(t * 16u + c, limit - 1u) * cHeads + cHead) * HD + 4u * g;
 #pragma unroll
-        for (int j = 0; j < NJ; j++) k[j] = *reinterpret_cast<const ab_f32x4*>(kp + 16 * j);
+        for (int j = 0; j < NJ; j++) k[j] = *reinterpret_cast<const raw4*>(kp + 16 * j);
     };
-    auto ask_v = [&](uint32_t t, ab_f32x4 (&v)[4][NV]) {
+    auto ask_v = [&](uint32_t t, raw4 (&v)[4][NV]) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const float* vp = vCache + ((size_t)min(t * 16u + 4u * g + i, limit - 1u) * numHeads + head) * HD + 4u * c;
+            const T* vp = vCache + ((size_t)min(t * 16u + 4u * g + i, limit - 1u) * cHeads + cHead) * HD + 4u * c;
 #pragma unroll
-            for (int jj = 0; jj < NV; jj++) v[i][jj] = *reinterpret_cast<const ab_f32x4*>(vp + 64 * jj);
+            for (int jj = 0; jj < NV; jj++) v[i][jj] = *reinterpret_cast<const raw4*>(vp + 64 * jj);
         }
     };
 
@@ -88,18 +101,20 @@ __global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const fl
     ab_f32x4 acc[4 * NV];
 #pragma unroll
     for (int a = 0; a < 4 * NV; a++) acc[a] = ab_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    ab_f32x4 kf[NJ], vf[4][NV];
+    raw4 kf[NJ], vf[4][NV];
     if (wave <= lastTile) ask_k(wave, kf);
     for (uint32_t t = wave; t <= lastTile; t += kAbWaves) {                        // (uniform in the wave)
         ask_v(t, vf);                                                              // in flight under the first product
         ab_f32x4 s0 = {0.0f, 0.0f, 0.0f, 0.0f}, s1 = s0;                           // two chains: one does not fill the pipe
 #pragma unroll
-        for (int j = 0; j < NJ; j += 2)
+        for (int j = 0; j < NJ; j += 2) {
+            const ab_f32x4 k0 = ab_widen(kf[j]), k1 = ab_widen(kf[j + 1]);
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j][e], q[j][e], s0, 0, 0, 0);
-                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j + 1][e], q[j + 1][e], s1, 0, 0, 0);
+                s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], q[j][e], s0, 0, 0, 0);
+                s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], q[j + 1][e], s1, 0, 0, 0);
             }
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (t + kAbWaves <= lastTile) ask_k(t + kAbWaves, kf);                     // the next tile's keys, under the second product
         __builtin_amdgcn_sched_barrier(0);
@@ -127,10 +142,12 @@ __global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const fl
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
-            for (int jj = 0; jj < NV; jj++)
+            for (int jj = 0; jj < NV; jj++) {
+                const ab_f32x4 v4 = ab_widen(vf[i][jj]);
 #pragma unroll
                 for (int e = 0; e < 4; e++)
-                    acc[4 * jj + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[i][jj][e], p[i], acc[4 * jj + e], 0, 0, 0);
+                    acc[4 * jj + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[e], p[i], acc[4 * jj + e], 0, 0, 0);
+            }
     }
 
     // merge: the four lanes of a query add their l in the order g = 0 .. 3, then the waves' states in the order w = 0, 1, ...
@@ -167,17 +184,32 @@ __global__ __launch_bounds__(64 * kAbWaves) void attention_block_kernel(const fl
     }
 }
 
-// the caller checked: 1 <= rows <= 64, pos0 + rows <= maxTokens <= 8192, headDim 64 / 128 / 256
-hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
-                                  uint32_t numHeads, uint32_t headDim, hipStream_t st) {
+template <typename T>
+static hipError_t launch_attention_block_on(const float* q, const T* kCache, const T* vCache, uint32_t pos0, uint32_t rows, float* out, uint32_t numHeads,
+                            uint32_t kvRep, uint32_t headDim, hipStream_t st) {
     const dim3 grid(numHeads, (rows + 15u) / 16u), block(64 * kAbWaves);
     switch (headDim) {
-        case 64: hipLaunchKernelGGL(attention_block_kernel<64>, grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads); break;
-        case 128: hipLaunchKernelGGL(attention_block_kernel<128>, grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads); break;
-        case 256: hipLaunchKernelGGL(attention_block_kernel<256>, grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads); break;
+        case 64: hipLaunchKernelGGL((attention_block_kernel<64, T>), grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads, kvRep); break;
+        case 128: hipLaunchKernelGGL((attention_block_kernel<128, T>), grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads, kvRep); break;
+        case 256: hipLaunchKernelGGL((attention_block_kernel<256, T>), grid, block, 0, st, q, kCache, vCache, pos0, rows, out, numHeads, kvRep); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+// This file is compiled twice (Makefile): as attention_block.o it holds the f32 instantiation, as attention_block_f16.o
+// (-DEFFORT_ATTENTION_BLOCK_F16) the one on the compact f16 cache.
+#ifndef EFFORT_ATTENTION_BLOCK_F16
+// the caller checked: 1 <= rows <= 64, pos0 + rows <= maxTokens <= 8192, headDim 64 / 128 / 256
+hipError_t launch_attention_block(const float* q, const float* kCache, const float* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                  uint32_t numHeads, uint32_t headDim, hipStream_t st) {
+    return launch_attention_block_on(q, kCache, vCache, pos0, rows, out, numHeads, 1u, headDim, st);
+}
+#else
+// the caller checked: 1 <= rows <= 64, pos0 + rows <= maxTokens <= 32768, kv16_shape_ok
+hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                      uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st) {
+    return launch_attention_block_on(q, kCache, vCache, pos0, rows, out, numHeads, numHeads / numHeadsKV, headDim, st);
+}
+#endif
 
 }  // namespace effort

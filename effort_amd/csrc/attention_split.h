@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
+#include <hip/hip_runtime.h>
 #define EFFORT_HD __host__ __device__
 #else
 #define EFFORT_HD
@@ -44,5 +45,37 @@ inline int attention_split_default(int numCU, int numHeadsKV, int maxTokens) {
     if (S > (int)kSplitMax) S = (int)kSplitMax;
     return S < 1 ? 1 : S;
 }
+
+// The compact f16 cache [maxTokens][numHeadsKV][headDim] (kv16.hip, the *_f16 entry points): the same head geometry, to
+// Mistral-7B's max_position_embeddings.
+constexpr int kKv16MaxTokens = 32768;
+inline bool kv16_shape_ok(int numHeads, int numHeadsKV, int headDim, int maxTokens) {
+    return maxTokens >= 1 && maxTokens <= kKv16MaxTokens && attention_split_shape_ok(numHeads, numHeadsKV, headDim);
+}
+
+#if defined(__HIPCC__)
+// ---- what the two split kernels (attention_split.hip on the f32 cache, kv16.hip on the f16 one) share on the device
+constexpr int kAsWaves = 4;
+
+template <int CTRL>
+__device__ __forceinline__ float as_row_shr_add(float x) {
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
+}
+// the sum over the LPK lanes of a key, in the key's LAST lane
+template <int LPK>
+__device__ __forceinline__ float as_key_sum(float x) {
+    x = as_row_shr_add<0x111>(x);
+    x = as_row_shr_add<0x112>(x);
+    x = as_row_shr_add<0x114>(x);
+    if constexpr (LPK >= 16) x = as_row_shr_add<0x118>(x);
+    if constexpr (LPK == 32) x += __shfl_xor(x, 16);
+    return x;
+}
+// Orders the wave's LDS writes before its later LDS reads for the compiler (a wave's LDS instructions execute in order).
+__device__ __forceinline__ void as_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+#endif
 
 }  // namespace effort

@@ -39,28 +39,6 @@
 
 namespace effort {
 
-constexpr int kAsWaves = 4;
-
-template <int CTRL>
-__device__ __forceinline__ float as_row_shr_add(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-// the sum over the LPK lanes of a key, in the key's LAST lane
-template <int LPK>
-__device__ __forceinline__ float as_key_sum(float x) {
-    x = as_row_shr_add<0x111>(x);
-    x = as_row_shr_add<0x112>(x);
-    x = as_row_shr_add<0x114>(x);
-    if constexpr (LPK >= 16) x = as_row_shr_add<0x118>(x);
-    if constexpr (LPK == 32) x += __shfl_xor(x, 16);
-    return x;
-}
-// Orders the wave's LDS writes before its later LDS reads for the compiler (a wave's LDS instructions execute in order).
-__device__ __forceinline__ void as_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <int HD, int R>
 __global__ __launch_bounds__(64 * kAsWaves) void attention_split_kernel(const float* __restrict__ q, const float* __restrict__ kCache,
                                                                         const float* __restrict__ vCache, const uint32_t* __restrict__ posPtr,
@@ -229,6 +207,11 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(const float* __res
     out[head * HD + d] = num / den;
 }
 
+hipError_t launch_attention_merge(const float* scratch, float* out, uint32_t numHeads, uint32_t headDim, uint32_t S, hipStream_t st) {
+    hipLaunchKernelGGL(attention_merge_kernel, dim3(numHeads), dim3(headDim), 0, st, scratch, out, S);
+    return hipGetLastError();
+}
+
 // the caller checked: R = numHeads / numHeadsKV in {1, 2, 4, 8}, headDim 64 / 128 / 256, 1 <= S <= kSplitMax, 1 <= maxTokens <= 8192
 hipError_t launch_attention_split(const float* q, const float* kCache, const float* vCache, const uint32_t* pos, float* out, float* scratch,
                                   uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t maxTokens, uint32_t S, hipStream_t st) {
@@ -244,8 +227,7 @@ hipError_t launch_attention_split(const float* q, const float* kCache, const flo
 #undef EFFORT_AS_CASE
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(attention_merge_kernel, dim3(numHeads), dim3(headDim), 0, st, scratch, out, S);
-    return hipGetLastError();
+    return launch_attention_merge(scratch, out, numHeads, headDim, S, st);
 }
 
 }  // namespace effort

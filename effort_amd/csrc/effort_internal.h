@@ -278,6 +278,23 @@ hipError_t launch_attention_block(const float* q, const float* kCache, const flo
 // decode attention with the keys split across workgroups and one cache copy read per KV group (attention_split.hip): two launches
 hipError_t launch_attention_split(const float* q, const float* kCache, const float* vCache, const uint32_t* pos, float* out, float* scratch,
                                   uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t maxTokens, uint32_t splits, hipStream_t st);
+// ... its second launch alone: the partial states of S splits in `scratch` merged into out (grid numHeads, block headDim)
+hipError_t launch_attention_merge(const float* scratch, float* out, uint32_t numHeads, uint32_t headDim, uint32_t S, hipStream_t st);
+
+// the compact f16 cache [maxTokens][numHeadsKV][headDim]: its writers and the split decode attention over it (kv16.hip: partial states
+// in launch_attention_split's layout, then launch_attention_merge), and the block attention (attention_block.hip: the f32 kernel
+// instantiated on the f16 element)
+hipError_t launch_rope_kv_f16(const float* xq, const float* xk, const float* xv, float* qOut, _Float16* kCache, _Float16* vCache,
+                              const uint32_t* pos, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, uint32_t maxTokens,
+                              int* status, hipStream_t st);
+hipError_t launch_rope_kv_rows_f16(const float* xq, const float* xk, const float* xv, float* qOut, _Float16* kCache, _Float16* vCache,
+                                   uint32_t pos0, uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase,
+                                   hipStream_t st);
+hipError_t launch_attention_split_f16(const float* q, const _Float16* kCache, const _Float16* vCache, const uint32_t* pos, float* out,
+                                      float* scratch, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t maxTokens,
+                                      uint32_t splits, hipStream_t st);
+hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                      uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
 
 // the sampled pick (sample.hip)
 hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,

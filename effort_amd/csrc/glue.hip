@@ -147,6 +147,32 @@ extern "C" int effort_attention_split(effort_ctx* c, const float* q, const float
     return HIP_RC(c, launch_attention_split(q, kCache, vCache, pos, out, scratch, (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim,
                                             (uint32_t)maxTokens, (uint32_t)S, c->stream));
 }
+// ---- the compact f16 cache [maxTokens][numHeadsKV][headDim] (kv16.hip; the block attention in attention_block.hip).  The argument VALUES are
+// judged before the pointers, as the prefill entry points judge theirs.
+static const char kKv16Shape[] = "headDim 64/128/256, numHeads / numHeadsKV 1/2/4/8, 1 <= maxTokens <= 32768";
+static int kv16_refuse(effort_ctx* c, const char* name, int code, const char* why) {
+    char what[128];
+    snprintf(what, sizeof(what), "%s: %s", name, why);
+    return fail(c, code, what);
+}
+extern "C" int effort_rope_kv_f16(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, void* kCache, void* vCache,
+                                  const uint32_t* pos, int numHeads, int numHeadsKV, int headDim, int maxTokens, float ropeBase) {
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens) || !(ropeBase > 1.0f)) return kv16_refuse(c, "rope_kv_f16", EFFORT_ERR_SHAPE, kKv16Shape);
+    if (!c || !xq || !xk || !xv || !qOut || !kCache || !vCache || !pos) return kv16_refuse(c, "rope_kv_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rope_kv_f16(xq, xk, xv, qOut, static_cast<_Float16*>(kCache), static_cast<_Float16*>(vCache), pos, (uint32_t)numHeads,
+                                        (uint32_t)numHeadsKV, (uint32_t)headDim, ropeBase, (uint32_t)maxTokens, c->d_status + 1, c->stream));
+}
+extern "C" int effort_attention_split_f16(effort_ctx* c, const float* q, const void* kCache, const void* vCache, const uint32_t* pos, float* out,
+                                          float* scratch, int numHeads, int numHeadsKV, int headDim, int maxTokens, int splits) {
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens)) return kv16_refuse(c, "attention_split_f16", EFFORT_ERR_SHAPE, kKv16Shape);
+    if (splits < 0 || splits > (int)kSplitMax) return kv16_refuse(c, "attention_split_f16", EFFORT_ERR_ARG, "0 <= splits <= 64");
+    if (!c || !q || !kCache || !vCache || !pos || !out || !scratch) return kv16_refuse(c, "attention_split_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    const int S = splits ? splits : attention_split_default(c->env.numCU, numHeadsKV, maxTokens);
+    return HIP_RC(c, launch_attention_split_f16(q, static_cast<const _Float16*>(kCache), static_cast<const _Float16*>(vCache), pos, out, scratch,
+                                                (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)maxTokens, (uint32_t)S, c->stream));
+}
 extern "C" int effort_debug_attention_split_range(int nTok, int splits, int split, int* tiles2) {
     if (nTok < 1 || splits < 1 || splits > (int)kSplitMax || split < 0 || split >= splits || !tiles2) return EFFORT_ERR_ARG;
     uint32_t t0, t1;
@@ -377,6 +403,25 @@ extern "C" int effort_attention_rows(effort_ctx* c, const float* q, const float*
 extern "C" int effort_attention_block(effort_ctx* c, const float* q, const float* kCache, const float* vCache, int pos0, int rows, float* out,
                                       int numHeads, int headDim, int maxTokens) {
     return prefill_attention(c, "attention_block", launch_attention_block, q, kCache, vCache, pos0, rows, out, numHeads, headDim, maxTokens);
+}
+// ... and their twins on the compact f16 cache: the same refusals in the same order, the shape being kv16_shape_ok's
+extern "C" int effort_rope_kv_rows_f16(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, void* kCache, void* vCache,
+                                       int pos0, int rows, int numHeads, int numHeadsKV, int headDim, int maxTokens, float ropeBase) {
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return kv16_refuse(c, "rope_kv_rows_f16", EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens) || !(ropeBase > 1.0f)) return kv16_refuse(c, "rope_kv_rows_f16", EFFORT_ERR_SHAPE, kKv16Shape);
+    if (!c || !xq || !xk || !xv || !qOut || !kCache || !vCache) return kv16_refuse(c, "rope_kv_rows_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rope_kv_rows_f16(xq, xk, xv, qOut, static_cast<_Float16*>(kCache), static_cast<_Float16*>(vCache), (uint32_t)pos0, (uint32_t)rows,
+                                             (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, ropeBase, c->stream));
+}
+extern "C" int effort_attention_block_f16(effort_ctx* c, const float* q, const void* kCache, const void* vCache, int pos0, int rows, float* out,
+                                          int numHeads, int numHeadsKV, int headDim, int maxTokens) {
+    if (!prefill_range_ok(pos0, rows, maxTokens)) return kv16_refuse(c, "attention_block_f16", EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens)) return kv16_refuse(c, "attention_block_f16", EFFORT_ERR_SHAPE, kKv16Shape);
+    if (!c || !q || !kCache || !vCache || !out) return kv16_refuse(c, "attention_block_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_attention_block_f16(q, static_cast<const _Float16*>(kCache), static_cast<const _Float16*>(vCache), (uint32_t)pos0, (uint32_t)rows, out,
+                                                (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, c->stream));
 }
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {
     if (!c || !gate || !idx2 || !val2 || n < 1) return fail(c, EFFORT_ERR_ARG, "top2_softmax: bad argument");

@@ -191,12 +191,27 @@ class Decoder:
     >= P through a second captured step (``token_step(split=True)``) whose attention is effort_rope_kv + effort_attention_split: the
     keys split across workgroups, one cache copy read per KV group (csrc/attention_split.hip), for every model kind and setting the
     step serves, dense included.  Same caches, same layout; logits within the f32 bar of the other step's, not its bits.  Needs
-    numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256 and maxTokens <= 8192; not with a column-sharded decoder."""
+    numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256 and maxTokens <= 8192; not with a column-sharded decoder.
+
+    ``kv_cache``: ``"f32"``, the default -- the caches are f32 [maxTokens][numHeads][headDim], every KV head stored once per query head
+    it serves, and everything above applies.  ``"f16"`` -- the compact caches, torch.float16 [maxTokens][numHeadsKV][headDim] (csrc/kv16.hip):
+    1 / (2 R) of the memory, R = numHeads / numHeadsKV, and maxTokens up to 32768.  EVERY token step's attention is then
+    effort_rope_kv_f16 + effort_attention_split_f16 (one captured step per effort, whatever ``fused_attention`` and the folded glue say)
+    and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"`` only).  Any model kind; K and V are
+    rounded to f16 on their way into the cache, nothing upstream of the rope changes.  Needs R in 1, 2, 4, 8 and headDim 64 / 128 / 256;
+    not with a column-sharded decoder, and not with ``split_attention_from`` (the split is implied)."""
 
     def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
                  world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False,
-                 split_attention_from: int | None = None):
+                 split_attention_from: int | None = None, kv_cache: str = "f32"):
         cfg = self.cfg = model.cfg
+        if kv_cache not in ("f32", "f16"):
+            raise ValueError(f"Decoder: kv_cache must be 'f32' or 'f16', not {kv_cache!r}")
+        self.kv16 = kv_cache == "f16"
+        if self.kv16 and split_attention_from is not None:
+            raise ValueError("Decoder: kv_cache='f16' implies the split attention at every position; leave split_attention_from out")
+        if self.kv16 and (sharded or emulate_world or int(world) > 1):
+            raise ValueError("Decoder: kv_cache='f16' is not implemented for the column-sharded decode loop")
         # A model with Q4 or core-only bundles (Model.random(q4=True) / Model.load(q4=True)).  token_step dispatches every multiply per
         # BUNDLE; an all-FP16 model is the case in which every bundle is a bucketed FP16 one.
         self.mixed = any(ew.q4 or not ew.bucketsLoaded for L in model.layers for ew in (L.wq, L.wk, L.wv, L.wo, L.w1, L.w2, L.w3))
@@ -269,8 +284,15 @@ class Decoder:
             self.gateOut, self.gateVals = f(cfg.numExperts), f(2)
             self.gateIdxs = torch.zeros(2, dtype=torch.int32, device=dev)
         self.logits = f(cfg.vocab)
-        self.kCache = [f(self.maxTokens, cfg.numHeads, cfg.headDim) for _ in range(cfg.numLayers)]     # xkLayerTokenHead
-        self.vCache = [f(self.maxTokens, cfg.numHeads, cfg.headDim) for _ in range(cfg.numLayers)]     # xvLayerToken
+        if self.kv16:
+            if (not 1 <= self.maxTokens <= 32768 or cfg.headDim not in (64, 128, 256) or cfg.numHeads % cfg.numHeadsKV
+                    or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8)):
+                raise ValueError("Decoder: kv_cache='f16' needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 32768")
+            cache = lambda: torch.zeros((self.maxTokens, cfg.numHeadsKV, cfg.headDim), dtype=torch.float16, device=dev)   # noqa: E731
+        else:
+            cache = lambda: f(self.maxTokens, cfg.numHeads, cfg.headDim)                                # noqa: E731
+        self.kCache = [cache() for _ in range(cfg.numLayers)]                                           # xkLayerTokenHead
+        self.vCache = [cache() for _ in range(cfg.numLayers)]                                           # xvLayerToken
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.tokId = torch.zeros(1, dtype=torch.int32, device=dev)
         self.history = torch.zeros(self.maxTokens, dtype=torch.int32, device=dev)
@@ -287,6 +309,13 @@ class Decoder:
             if (self.split_attention_from < 0 or splits < 1 or nbytes <= 0 or self.maxTokens > 8192 or cfg.numHeads % cfg.numHeadsKV
                     or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8)):
                 raise ValueError("Decoder: split_attention_from >= 0 needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 8192")
+            self.splitScratch = f(nbytes // 4)
+        if self.kv16:                                     # (the scratch as above: the f16 kernel leaves the same partial states)
+            lib = _lib.lib()
+            splits = lib.effort_attention_split_default_splits(self.g.ctx, cfg.numHeadsKV, self.maxTokens)
+            nbytes = lib.effort_attention_split_scratch_bytes(cfg.numHeads, cfg.headDim, splits) if splits >= 1 else 0
+            if nbytes <= 0:
+                raise ValueError(f"Decoder: kv_cache='f16': the library resolved no split count for this shape (default splits {splits})")
             self.splitScratch = f(nbytes // 4)
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
         self._pf = None                                   # prefill's block buffers: made by the first ``prefill`` (see ``_prefill_buffers``)
@@ -331,6 +360,8 @@ class Decoder:
         ``split``: every layer's attention is effort_rope_kv + effort_attention_split (three launches: the cache write, the partial
         states, their merge) whatever ``fused_attention`` and the folded glue say; a Decoder made with ``split_attention_from``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
+        if split and self.kv16:
+            raise ValueError("Decoder.token_step(split=True): a kv_cache='f16' decoder's only step is already the split one; leave split out")
         if split and self.splitScratch is None:
             raise ValueError("Decoder.token_step(split=True): make the Decoder with split_attention_from")
         g._bind_stream()
@@ -392,7 +423,12 @@ class Decoder:
 
         def attention(n):                                  # xq_temp, xk_temp, xv_temp -> attnOutput, the caches at pos written
             kc, vc, rope = _p(self.kCache[n]), _p(self.vCache[n]), C.c_float(cfg.ropeBase)
-            if split or self._two_launch_attention[bool(dense)]:
+            if self.kv16:                                  # the compact f16 caches: one path at every position
+                ck(lib.effort_rope_kv_f16(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
+                                          cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_f16")
+                ck(lib.effort_attention_split_f16(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), _p(self.splitScratch),
+                                                  cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, 0), "attention_split_f16")
+            elif split or self._two_launch_attention[bool(dense)]:
                 ck(lib.effort_rope_kv(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
                                       cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv")
                 if split:
@@ -624,7 +660,8 @@ class Decoder:
         ``attention``: ``"rows"`` is effort_attention_rows (every query of a block reads its keys and values again; the token step's
         bits); ``"block"`` puts effort_attention_block in its place, same operands -- the block's queries share each K / V tile, f32
         MFMA with an online softmax, within the f32 bar of the same float64 value but not the same bits.  On either path the caches
-        do not depend on ``chunk``.
+        do not depend on ``chunk``.  A ``kv_cache="f16"`` decoder has no rows kernel: it takes ``"block"`` alone, through
+        effort_rope_kv_rows_f16 + effort_attention_block_f16.
 
         ``ffn``: ``"dense"``, the default, is the walk above and serves dense-FFN models only.  ``"routed"`` serves a Mixtral model (FP16,
         an ffnGate in every layer, numExperts >= 2, the expert stacks' cores [E, out, in] kept): the second half of a layer becomes
@@ -695,8 +732,15 @@ class Decoder:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
         if attention not in ("rows", "block"):
             raise ValueError(f"Decoder.prefill: attention must be 'rows' or 'block', not {attention!r}")
-        attend, attendName = ((lib.effort_attention_rows, "attention_rows") if attention == "rows" else
-                              (lib.effort_attention_block, "attention_block"))
+        if self.kv16 and attention != "block":
+            raise ValueError("Decoder.prefill: a kv_cache='f16' decoder prefills with attention='block' (there is no rows kernel for the f16 cache)")
+        kvh = (cfg.numHeadsKV,) if self.kv16 else ()       # (the f16 entry points take the KV heads: the cache holds them alone)
+        if self.kv16:
+            rope_rows, attend, attendName = lib.effort_rope_kv_rows_f16, lib.effort_attention_block_f16, "attention_block_f16"
+        else:
+            rope_rows = lib.effort_rope_kv_rows
+            attend, attendName = ((lib.effort_attention_rows, "attention_rows") if attention == "rows" else
+                                  (lib.effort_attention_block, "attention_block"))
         g._bind_stream()
         if from_buckets:                                   # (the last refusal: the library looks at each handle's buckets once and remembers)
             for ew in bundles:
@@ -728,11 +772,11 @@ class Decoder:
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(delta), _p(L.attnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 for ew, out in ((L.wq, self.pf_xq_temp), (L.wk, self.pf_xk_temp), (L.wv, self.pf_xv_temp)):
                     mul(self.pf_norm, ew, out, rows)
-                ck(lib.effort_rope_kv_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
-                                           cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
+                ck(rope_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
+                             cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
                 if n == len(m.layers) - 1:
                     break                                  # nothing after the last layer's cache write reaches a cache
-                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, cfg.headDim, self.maxTokens), attendName)
+                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, *kvh, cfg.headDim, self.maxTokens), attendName)
                 mul(self.pf_attnOutput, L.wo, self.pf_attnFfnOut, rows)
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 if routed:

@@ -337,6 +337,32 @@ EFFORT_API int effort_attention_split_default_splits(effort_ctx* ctx, int numHea
 EFFORT_API int effort_attention_split(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev,
                            const uint32_t* pos_dev, float* out_dev, float* scratch_dev, int numHeads, int numHeadsKV, int headDim,
                            int maxTokens, int splits);
+/* ---- the compact f16 KV cache (opt-in; nothing above reads or writes it) ----
+ * K and V each f16 [maxTokens][numHeadsKV][headDim], row t = token t, KV head g serving query heads g * R .. g * R + R - 1,
+ * R = numHeads / numHeadsKV: 1 / (2 R) of the f32 cache's memory.  Its entry points -- the two below, effort_rope_kv_rows_f16 and
+ * effort_attention_block_f16 further down -- take maxTokens 1 .. 32768, headDim 64 / 128 / 256 and R 1 / 2 / 4 / 8; anything else returns
+ * EFFORT_ERR_SHAPE.  The argument VALUES are judged before the pointers (a null pointer: EFFORT_ERR_ARG), nothing is enqueued by a refusal.
+ *
+ * effort_rope_kv_f16: effort_rope_kv's arguments and rope with the two caches in this format.  q_out_dev receives effort_rope_kv's bits;
+ * row *pos_dev of k_cache receives half_rn (round to nearest even, overflow to +-inf) of the f32 value effort_rope_kv stores for the KV
+ * head, row *pos_dev of v_cache half_rn(xv); each element is written once, no other row is touched.  A step at *pos_dev >= maxTokens
+ * writes nothing and raises bit 0 of the decode status.  ropeBase <= 1: EFFORT_ERR_SHAPE.
+ *
+ * effort_attention_split_f16: effort_attention_split over this format -- the same two launches, grid, key ranges per split (from *pos_dev,
+ * on the device), scratch (effort_attention_split_scratch_bytes; holds no state between calls), resolution of splits = 0
+ * (effort_attention_split_default_splits) and merge; capturable, one captured call serves every position.  The halves are widened in
+ * registers, q stays f32 and both products are f32 multiply-adds: against the float64 attention over the f16 values the cache HOLDS, every
+ * element is within 2e-5 * max|out|, cos-sim >= 0.999999 (effort_attention_split's bar; what storing K / V as f16 costs a model's logits is
+ * in DESIGN 4.4c).  No cache row past *pos_dev is read.  The output's bits are a function of q, cache rows 0 .. *pos_dev, *pos_dev, the
+ * resolved splits and R; they are identical run to run.  A V element stored as +-inf makes the outputs it reaches non-finite (inf or NaN).
+ * Refusals in this order: the shape EFFORT_ERR_SHAPE; splits outside 0 .. 64
+ * EFFORT_ERR_ARG; a null argument (scratch_dev included) EFFORT_ERR_ARG. */
+EFFORT_API int effort_rope_kv_f16(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
+                       void* k_cache_f16_dev, void* v_cache_f16_dev, const uint32_t* pos_dev, int numHeads, int numHeadsKV, int headDim,
+                       int maxTokens, float ropeBase);
+EFFORT_API int effort_attention_split_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev,
+                               const uint32_t* pos_dev, float* out_dev, float* scratch_dev, int numHeads, int numHeadsKV, int headDim,
+                               int maxTokens, int splits);
 /* silu(x1, x3, out:) = x3 * x1 / (1 + exp(-x1)) (matrix.metal:25-35). */
 EFFORT_API int effort_silu_mul(effort_ctx* ctx, const float* x1_dev, const float* x3_dev, float* out_dev, int n);
 /* tokEmbeddings.fetchRow(id, out:) (aux.metal:355): row *id_dev of an f16 [vocab][n] table as f32. */
@@ -517,6 +543,20 @@ EFFORT_API int effort_attention_rows(effort_ctx* ctx, const float* q_dev, const 
  * written.  It needs the block's effort_rope_kv_rows to have completed: enqueue both on the context's stream. */
 EFFORT_API int effort_attention_block(effort_ctx* ctx, const float* q_dev, const float* k_cache_dev, const float* v_cache_dev, int pos0, int rows,
                            float* out_dev, int numHeads, int headDim, int maxTokens);
+/* The block forms on the compact f16 cache (see effort_rope_kv_f16 for the format and the shapes).
+ * effort_rope_kv_rows_f16: effort_rope_kv_f16 with row r roped at position pos0 + r: per row its bits, q_out included; cache rows
+ *   pos0 .. pos0 + rows - 1 are written, no other.  Operand layouts and range checks as effort_rope_kv_rows.
+ * effort_attention_block_f16: effort_attention_block with head h reading KV head h / R of the f16 caches, widened in registers: the
+ *   same workgroups, lane maps, f32 MFMA products, order of the sums and bar (against float64 over the f16 values the cache holds).  So
+ *   an output row's bits are, as there, a function of the query, its absolute position pos0 + r and cache rows 0 .. pos0 + r -- not of
+ *   pos0, rows or r on their own.  No cache row at or past pos0 + rows and no q row at or past rows is read.
+ * Refusals in this order: rows outside 1 .. 64, pos0 < 0, pos0 + rows > maxTokens EFFORT_ERR_ARG; the shape EFFORT_ERR_SHAPE; a null
+ * pointer EFFORT_ERR_ARG. */
+EFFORT_API int effort_rope_kv_rows_f16(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
+                            void* k_cache_f16_dev, void* v_cache_f16_dev, int pos0, int rows, int numHeads, int numHeadsKV, int headDim,
+                            int maxTokens, float ropeBase);
+EFFORT_API int effort_attention_block_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev, int pos0,
+                               int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
 
 /* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */
 

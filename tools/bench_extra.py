@@ -20,7 +20,9 @@ the generation rules -- penalties, bias, min-p, stop ids: effort_logit_rules -- 
 argmax_kernel and sample_kernel; its record also goes to profiles/r14_decode_rules.json; standalone too) and `decode_attention_split`
 (a decode step's attention by position: the one- and two-launch attention beside effort_attention_split on rotating caches, and the
 decode loop from position 4000 and from 0 with and without `split_attention_from`; its record also goes to
-profiles/r15_attention_split.json; standalone too).
+profiles/r15_attention_split.json; standalone too) and `decode_kv16` (the compact f16 KV cache beside the f32 one: effort_rope_kv +
+effort_attention_split against the _f16 pair by position, to 32767 for the f16 pair, and Mistral-7B-shaped decodes with
+split_attention_from=0 against kv_cache="f16" with the caches' memory; its record also goes to profiles/r16_kv16.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -38,8 +40,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1135,6 +1137,112 @@ def decode_attention_split(b, res):
     del decs, model
 
 
+def decode_kv16(b, res):
+    """The compact f16 KV cache (csrc/kv16.hip) beside the f32 one, one process, the legs' windows alternating.  Kernel legs,
+    decode_attention_split's protocol: 32 heads, 8 KV heads, headDim 128, four ROTATING f32 cache pairs (walked twice) and eight f16 ones per graph (the same live bytes, eight steps either way), device events; effort_rope_kv
+    + effort_attention_split on f32 caches against effort_rope_kv_f16 + effort_attention_split_f16, default splits, maxTokens 8192 for both
+    at the shared positions; position 32767 (maxTokens 32768) for the f16 pair alone.  Model legs, Mistral-7B shapes, 25 % effort: tokens/s
+    over 64 captured steps from position 4000 (after a `prefill(attention="block")` of 4000 tokens) and from position 0,
+    split_attention_from=0 against kv_cache="f16", and what torch.cuda.memory_allocated grows by when each Decoder is made."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(83)
+    nh, nkv, hd, pairs, rope = 32, 8, 128, 4, C.c_float(1e6)
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    c32 = [(rnd(8192, nh, hd), rnd(8192, nh, hd)) for _ in range(pairs)]
+    # (twice the pairs: the f16 leg then rotates through the bytes the f32 leg rotates through at every shared position, so a last-level
+    #  cache serves neither leg's rotation better than the other's; the f32 leg walks its four pairs twice, so both graphs hold eight steps)
+    c16 = [(rnd(32768, nkv, hd).half(), rnd(32768, nkv, hd).half()) for _ in range(2 * pairs)]
+    xq, xk, xv, qr, out = rnd(nh * hd), rnd(nkv * hd), rnd(nkv * hd), rnd(nh * hd), torch.zeros(nh * hd, device=b.dev)
+    scratch = torch.zeros(lib.effort_attention_split_scratch_bytes(nh, hd, 64) // 4, device=b.dev)
+    posd = torch.zeros(1, dtype=torch.int32, device=b.dev)
+
+    def leg(f16, maxTokens):
+        ropeKv, split = (lib.effort_rope_kv_f16, lib.effort_attention_split_f16) if f16 else (lib.effort_rope_kv, lib.effort_attention_split)
+
+        def fn():
+            g._bind_stream()
+            for kc, vc in (c16 if f16 else c32 + c32):                           # eight calls per graph either way
+                g.check(ropeKv(g.ctx, p(xq), p(xk), p(xv), p(qr), p(kc), p(vc), p(posd), nh, nkv, hd, maxTokens, rope), "rope_kv")
+                g.check(split(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), p(scratch), nh, nkv, hd, maxTokens, 0), "attention_split")
+        return fn
+    kern = {"protocol": "a step's attention (cache write, partial states, merge: three launches either way) on rotating cache pairs, 4 of f32 walked twice / 8 of f16 (the same "
+                        "bytes live, eight steps per graph either way), 4 replays per window, best of 3 windows, device events, the legs' windows alternating; kv_bytes = live rows x the "
+                        "K + V bytes a row of one copy per KV group holds (8 KB f32, 4 KB f16) + the partial states written and read",
+            "heads": nh, "headsKV": nkv, "headDim": hd}
+    for pos in (63, 255, 1023, 4095, 8191, 32767):
+        maxTokens = 8192 if pos < 8192 else 32768
+        legs = {"f16": leg(True, maxTokens)}
+        if pos < 8192:
+            legs["f32"] = leg(False, maxTokens)
+        posd.fill_(pos)
+        S = lib.effort_attention_split_default_splits(g.ctx, nkv, maxTokens)
+        us, row = alternating_us(b, legs, 1), {"maxTokens": maxTokens, "splits": S}
+        us = {name: t / (2 * pairs) for name, t in us.items()}
+        for name, t in us.items():
+            asked = (pos + 1) * hd * (2 if name == "f16" else 4) * 2 * nkv + 2 * nh * S * (hd + 2) * 4
+            row[name] = {"us_per_step": round(t, 2), "kv_bytes": asked, "TBps_of_kv_bytes": round(asked / t / 1e6, 3)}
+        if "f32" in us:
+            row["f32_over_f16_time"] = round(us["f32"] / us["f16"], 3)
+        kern[f"pos_{pos}"] = row
+    del c32, c16
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (4000,), generator=torch.Generator().manual_seed(3))]
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "effort": 0.25, "maxTokens": 4096,
+         "protocol": "each Decoder's step graph captured, then Decoder.prefill(attention='block') of 4000 tokens; per leg the position is set, 4 warm "
+                     "replays, the position set again, 64 replays between synchronised wall-clock reads, best of 2; 'f32' replays the split step of a "
+                     "Decoder made with split_attention_from=0, 'f16' the step of one made with kv_cache='f16'; *_decoder_bytes = what "
+                     "torch.cuda.memory_allocated grew by over the Decoder's construction (the caches and a few MB of state), *_cache_bytes = "
+                     "the cache tensors alone"}
+    decs = {}
+    for name, how in (("f32", dict(split_attention_from=0)), ("f16", dict(kv_cache="f16"))):
+        before = torch.cuda.memory_allocated()
+        dec = Decoder(model, maxTokens=4096, **how)
+        m[f"{name}_decoder_bytes"] = int(torch.cuda.memory_allocated() - before)
+        m[f"{name}_cache_bytes"] = int(sum(c.numel() * c.element_size() for c in dec.kCache + dec.vCache))
+        gr = dec._graph(0.25, False, split=name == "f32")
+        B._GRAPHS_FOR_LIFE.extend(dec._graphs.values())
+        dec.prefill(prompt, attention="block")
+        decs[name] = (dec, gr)
+    for start in (4000, 0):
+        for name in ("f32", "f16", "f32"):
+            dec, gr = decs[name]
+            best = float("inf")
+            for _ in range(2):
+                for steps in (4, 64):
+                    dec.pos.fill_(start)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(steps):
+                        gr.replay()
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                best = min(best, dt)
+            key = f"from_{start}_{name}_tokens_per_s"
+            m[key + "_again" if key in m else key] = round(64 / best, 1)
+        m[f"from_{start}_f16_over_f32"] = round(m[f"from_{start}_f16_tokens_per_s"] / m[f"from_{start}_f32_tokens_per_s"], 3)
+    m["decode_status"] = [dec.status() for dec, _ in decs.values()]
+    res_out["model"] = m
+    res["decode_kv16"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r16_kv16.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del decs, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1152,7 +1260,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
-       "decode_attention_split": decode_attention_split}
+       "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16}
 
 
 class Light:

@@ -85,6 +85,12 @@ _SIGS = {
     "effort_attention_split_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "effort_rope_kv_rows_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "effort_attention_block_f16": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "effort_rope_kv_ring": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "effort_attention_window_default_splits": (C.c_int, [_P, C.c_int, C.c_int]),
+    "effort_attention_window": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "effort_debug_attention_window_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "effort_rope_kv_rows_ring": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "effort_attention_block_window": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "effort_silu_mul": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "effort_fetch_row": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "effort_argmax": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int]),

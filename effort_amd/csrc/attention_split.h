@@ -25,6 +25,18 @@ EFFORT_HD inline void attention_split_tiles(uint32_t nTok, uint32_t S, uint32_t 
     t1 = (s + 1u) * per < nTiles ? (s + 1u) * per : nTiles;
 }
 
+// The same rule over a WINDOW of keys (kv_window.hip): the query at position pos sees tokens lo .. pos, lo = max(0, pos + 1 - window).
+// The tiles stay on absolute multiples of kSplitTile counted from token 0; the live ones are tLo = lo / 64 .. tHi = pos / 64, and split
+// s takes per = ceil(live tiles / S) consecutive ones from tLo + s per.  With lo = 0 this is attention_split_tiles(pos + 1, ...).
+EFFORT_HD inline uint32_t attention_window_lo(uint32_t pos, uint32_t window) { return pos >= window ? pos - window + 1u : 0u; }
+EFFORT_HD inline void attention_window_tiles(uint32_t pos, uint32_t window, uint32_t S, uint32_t s, uint32_t& t0, uint32_t& t1) {
+    const uint32_t tLo = attention_window_lo(pos, window) / kSplitTile;
+    const uint32_t nTiles = pos / kSplitTile - tLo + 1u;
+    const uint32_t per = (nTiles + S - 1u) / S;
+    t0 = tLo + (s * per < nTiles ? s * per : nTiles);
+    t1 = tLo + ((s + 1u) * per < nTiles ? (s + 1u) * per : nTiles);
+}
+
 // The scratch of a call, in floats: acc [numHeads][S][headDim], then (m, l) [numHeads][S][2].
 EFFORT_HD inline size_t attention_split_scratch_floats(uint32_t numHeads, uint32_t headDim, uint32_t S) {
     return (size_t)numHeads * S * (headDim + 2u);
@@ -51,6 +63,14 @@ inline int attention_split_default(int numCU, int numHeadsKV, int maxTokens) {
 constexpr int kKv16MaxTokens = 32768;
 inline bool kv16_shape_ok(int numHeads, int numHeadsKV, int headDim, int maxTokens) {
     return maxTokens >= 1 && maxTokens <= kKv16MaxTokens && attention_split_shape_ok(numHeads, numHeadsKV, headDim);
+}
+
+// The rolling cache [ringRows][numHeadsKV][headDim] (kv_window.hip, the *_ring / *_window entry points): token t in row t % ringRows, a
+// query sees `window` keys including its own.  A block of `rows` tokens needs window + rows - 1 ring rows (rows = 1: a token step).
+constexpr int kWindowMaxPos = 1048576;       // positions stay exact as f32 in the rope
+inline bool kv_window_shape_ok(int numHeads, int numHeadsKV, int headDim, int ringRows, int window, int rows) {
+    return window >= 1 && window <= ringRows && ringRows <= kKv16MaxTokens && window - 1 <= ringRows - rows &&
+           attention_split_shape_ok(numHeads, numHeadsKV, headDim);
 }
 
 #if defined(__HIPCC__)

@@ -296,6 +296,21 @@ hipError_t launch_attention_split_f16(const float* q, const _Float16* kCache, co
 hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
                                       uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
 
+// the rolling f16 cache [ringRows][numHeadsKV][headDim], token t in row t % ringRows, with sliding-window attention over it
+// (kv_window.hip): the writers, the windowed split decode attention (launch_attention_split's scratch and merge) and block attention
+hipError_t launch_rope_kv_ring(const float* xq, const float* xk, const float* xv, float* qOut, _Float16* kRing, _Float16* vRing,
+                               const uint32_t* pos, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase, uint32_t ringRows,
+                               uint32_t maxPos, int* status, hipStream_t st);
+hipError_t launch_rope_kv_rows_ring(const float* xq, const float* xk, const float* xv, float* qOut, _Float16* kRing, _Float16* vRing,
+                                    uint32_t pos0, uint32_t rows, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, float ropeBase,
+                                    uint32_t ringRows, hipStream_t st);
+hipError_t launch_attention_window(const float* q, const _Float16* kRing, const _Float16* vRing, const uint32_t* pos, float* out, float* scratch,
+                                   uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t ringRows, uint32_t window, uint32_t splits,
+                                   hipStream_t st);
+hipError_t launch_attention_block_window(const float* q, const _Float16* kRing, const _Float16* vRing, uint32_t pos0, uint32_t rows, float* out,
+                                         uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t ringRows, uint32_t window,
+                                         hipStream_t st);
+
 // the sampled pick (sample.hip)
 hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,
                          int* status, uint32_t* topkIdx, float* topkVal, hipStream_t st);

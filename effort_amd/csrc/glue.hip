@@ -180,6 +180,38 @@ extern "C" int effort_debug_attention_split_range(int nTok, int splits, int spli
     tiles2[0] = (int)t0; tiles2[1] = (int)t1;
     return EFFORT_OK;
 }
+// ---- the rolling f16 cache with sliding-window attention (kv_window.hip): values before pointers, as above
+static const char kWindowShape[] = "headDim 64/128/256, numHeads / numHeadsKV 1/2/4/8, 1 <= window <= ringRows <= 32768 (a block: window + rows - 1 <= ringRows), positions <= 1048576";
+extern "C" int effort_rope_kv_ring(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, void* kRing, void* vRing,
+                                   const uint32_t* pos, int numHeads, int numHeadsKV, int headDim, int ringRows, int maxPos, float ropeBase) {
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, ringRows) || maxPos < 1 || maxPos > kWindowMaxPos || !(ropeBase > 1.0f))
+        return kv16_refuse(c, "rope_kv_ring", EFFORT_ERR_SHAPE, "headDim 64/128/256, numHeads / numHeadsKV 1/2/4/8, 1 <= ringRows <= 32768, 1 <= maxPos <= 1048576");
+    if (!c || !xq || !xk || !xv || !qOut || !kRing || !vRing || !pos) return kv16_refuse(c, "rope_kv_ring", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rope_kv_ring(xq, xk, xv, qOut, static_cast<_Float16*>(kRing), static_cast<_Float16*>(vRing), pos, (uint32_t)numHeads,
+                                         (uint32_t)numHeadsKV, (uint32_t)headDim, ropeBase, (uint32_t)ringRows, (uint32_t)maxPos, c->d_status + 1, c->stream));
+}
+extern "C" int effort_attention_window_default_splits(effort_ctx* c, int numHeadsKV, int window) {
+    if (!c || numHeadsKV <= 0 || window <= 0 || window > kKv16MaxTokens) return EFFORT_ERR_ARG;
+    return attention_split_default(c->env.numCU, numHeadsKV, window + (int)kSplitTile);
+}
+extern "C" int effort_attention_window(effort_ctx* c, const float* q, const void* kRing, const void* vRing, const uint32_t* pos, float* out,
+                                       float* scratch, int numHeads, int numHeadsKV, int headDim, int ringRows, int window, int splits) {
+    if (!kv_window_shape_ok(numHeads, numHeadsKV, headDim, ringRows, window, 1)) return kv16_refuse(c, "attention_window", EFFORT_ERR_SHAPE, kWindowShape);
+    if (splits < 0 || splits > (int)kSplitMax) return kv16_refuse(c, "attention_window", EFFORT_ERR_ARG, "0 <= splits <= 64");
+    if (!c || !q || !kRing || !vRing || !pos || !out || !scratch) return kv16_refuse(c, "attention_window", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    const int S = splits ? splits : attention_split_default(c->env.numCU, numHeadsKV, window + (int)kSplitTile);
+    return HIP_RC(c, launch_attention_window(q, static_cast<const _Float16*>(kRing), static_cast<const _Float16*>(vRing), pos, out, scratch,
+                                             (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)ringRows, (uint32_t)window, (uint32_t)S, c->stream));
+}
+extern "C" int effort_debug_attention_window_range(int pos, int window, int splits, int split, int* tiles2) {
+    if (pos < 0 || window < 1 || splits < 1 || splits > (int)kSplitMax || split < 0 || split >= splits || !tiles2) return EFFORT_ERR_ARG;
+    uint32_t t0, t1;
+    attention_window_tiles((uint32_t)pos, (uint32_t)window, (uint32_t)splits, (uint32_t)split, t0, t1);
+    tiles2[0] = (int)t0; tiles2[1] = (int)t1;
+    return EFFORT_OK;
+}
 extern "C" int effort_silu_mul(effort_ctx* c, const float* x1, const float* x3, float* out, int n) {
     if (!c || !x1 || !x3 || !out || n <= 0) return fail(c, EFFORT_ERR_ARG, "silu_mul: bad argument");
     JOIN_TRY(c);
@@ -422,6 +454,27 @@ extern "C" int effort_attention_block_f16(effort_ctx* c, const float* q, const v
     JOIN_TRY(c);
     return HIP_RC(c, launch_attention_block_f16(q, static_cast<const _Float16*>(kCache), static_cast<const _Float16*>(vCache), (uint32_t)pos0, (uint32_t)rows, out,
                                                 (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, c->stream));
+}
+// ... and the block forms on the rolling cache: rows and pos0 first (the range of positions is part of the shape), then the shape
+extern "C" int effort_rope_kv_rows_ring(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, void* kRing, void* vRing,
+                                        int pos0, int rows, int numHeads, int numHeadsKV, int headDim, int ringRows, float ropeBase) {
+    if (!prefill_rows_ok(rows) || pos0 < 0) return kv16_refuse(c, "rope_kv_rows_ring", EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0");
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, ringRows) || rows > ringRows || pos0 > kWindowMaxPos - rows || !(ropeBase > 1.0f))
+        return kv16_refuse(c, "rope_kv_rows_ring", EFFORT_ERR_SHAPE, "headDim 64/128/256, numHeads / numHeadsKV 1/2/4/8, rows <= ringRows <= 32768, pos0 + rows <= 1048576");
+    if (!c || !xq || !xk || !xv || !qOut || !kRing || !vRing) return kv16_refuse(c, "rope_kv_rows_ring", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rope_kv_rows_ring(xq, xk, xv, qOut, static_cast<_Float16*>(kRing), static_cast<_Float16*>(vRing), (uint32_t)pos0, (uint32_t)rows,
+                                              (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, ropeBase, (uint32_t)ringRows, c->stream));
+}
+extern "C" int effort_attention_block_window(effort_ctx* c, const float* q, const void* kRing, const void* vRing, int pos0, int rows, float* out,
+                                             int numHeads, int numHeadsKV, int headDim, int ringRows, int window) {
+    if (!prefill_rows_ok(rows) || pos0 < 0) return kv16_refuse(c, "attention_block_window", EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0");
+    if (!kv_window_shape_ok(numHeads, numHeadsKV, headDim, ringRows, window, rows) || pos0 > kWindowMaxPos - rows)
+        return kv16_refuse(c, "attention_block_window", EFFORT_ERR_SHAPE, kWindowShape);
+    if (!c || !q || !kRing || !vRing || !out) return kv16_refuse(c, "attention_block_window", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_attention_block_window(q, static_cast<const _Float16*>(kRing), static_cast<const _Float16*>(vRing), (uint32_t)pos0, (uint32_t)rows, out,
+                                                   (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)ringRows, (uint32_t)window, c->stream));
 }
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {
     if (!c || !gate || !idx2 || !val2 || n < 1) return fail(c, EFFORT_ERR_ARG, "top2_softmax: bad argument");

@@ -29,35 +29,11 @@
 // output's bits are a function of q, cache rows 0 .. pos, pos, S and R, and repeat run to run.
 #include "attention_split.h"
 #include "effort_internal.h"
+#include "kv16_device.h"
 
 namespace effort {
 
 // ---- writers
-// One vector x of headDim values roped at pos, block = headDim: rope_kv_row's expression (decode.hip), term for term.
-__device__ __forceinline__ float rope_row(const float* __restrict__ x, uint32_t pos, float logBase) {
-    const uint32_t d = threadIdx.x, half = blockDim.x / 2;
-    const uint32_t j = d % half;
-    const float freq = (float)exp((double)logBase * (-(double)j / (double)half));          // Float(freq), model.swift:707
-    const float angle = (float)pos * freq;
-    const float c = cosf(angle), s = sinf(angle);
-    return d < half ? x[d] * c - x[d + half] * s : x[d] * c + x[d - half] * s;
-}
-// Row `row` of the token at position pos; xq, xk, xv and qOut are the token's vectors.
-__device__ __forceinline__ void rope_kv_f16_row(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
-                                                float* __restrict__ qOut, _Float16* __restrict__ kCache, _Float16* __restrict__ vCache,
-                                                uint32_t pos, uint32_t row, uint32_t numHeads, uint32_t numHeadsKV, float logBase) {
-    const uint32_t d = threadIdx.x, headDim = blockDim.x;
-    if (row < numHeads) {                              // (uniform)
-        qOut[row * headDim + d] = rope_row(xq + row * headDim, pos, logBase);
-        return;
-    }
-    const uint32_t g = row - numHeads;
-    float kr = rope_row(xk + g * headDim, pos, logBase);
-    asm volatile("" : "+v"(kr));                       // the f32 value first, then ONE conversion: no mixed-precision fold of the two
-    const size_t slot = ((size_t)pos * numHeadsKV + g) * headDim + d;
-    kCache[slot] = (_Float16)kr;                       // v_cvt_f16_f32: round to nearest even, overflow to +-inf
-    vCache[slot] = (_Float16)xv[g * headDim + d];
-}
 __global__ void rope_kv_f16_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
                                    float* __restrict__ qOut, _Float16* __restrict__ kCache, _Float16* __restrict__ vCache,
                                    const uint32_t* __restrict__ posPtr, uint32_t numHeads, uint32_t numHeadsKV, float logBase,
@@ -67,39 +43,18 @@ __global__ void rope_kv_f16_kernel(const float* __restrict__ xq, const float* __
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, 1);
         return;
     }
-    rope_kv_f16_row(xq, xk, xv, qOut, kCache, vCache, pos, blockIdx.x, numHeads, numHeadsKV, logBase);
+    rope_kv_f16_row(xq, xk, xv, qOut, kCache, vCache, pos, pos, blockIdx.x, numHeads, numHeadsKV, logBase);
 }
 // row blockIdx.y of the block at position pos0 + blockIdx.y (no guard: the host checked the range)
 __global__ void rope_kv_rows_f16_kernel(const float* __restrict__ xq, const float* __restrict__ xk, const float* __restrict__ xv,
                                         float* __restrict__ qOut, _Float16* __restrict__ kCache, _Float16* __restrict__ vCache,
                                         uint32_t pos0, uint32_t numHeads, uint32_t numHeadsKV, float logBase) {
     const size_t qOff = (size_t)blockIdx.y * numHeads * blockDim.x, kvOff = (size_t)blockIdx.y * numHeadsKV * blockDim.x;
-    rope_kv_f16_row(xq + qOff, xk + kvOff, xv + kvOff, qOut + qOff, kCache, vCache, pos0 + blockIdx.y, blockIdx.x, numHeads, numHeadsKV, logBase);
+    rope_kv_f16_row(xq + qOff, xk + kvOff, xv + kvOff, qOut + qOff, kCache, vCache, pos0 + blockIdx.y, pos0 + blockIdx.y, blockIdx.x,
+                    numHeads, numHeadsKV, logBase);
 }
 
 // ---- the split decode attention
-typedef _Float16 kv_half2 __attribute__((ext_vector_type(2)));
-
-// W 32-bit words (2 W halves) of a cache row in one load: 16 bytes (W = 4) or 8 (W = 2)
-template <int W>
-__device__ __forceinline__ void kv_load(const _Float16* __restrict__ p, uint32_t (&w)[W]) {
-    if constexpr (W == 4) {
-        const uint4 t = *reinterpret_cast<const uint4*>(p);
-        w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
-    } else {
-        const uint2 t = *reinterpret_cast<const uint2*>(p);
-        w[0] = t.x; w[1] = t.y;
-    }
-}
-template <int W>
-__device__ __forceinline__ void kv_widen(const uint32_t (&w)[W], float (&f)[2 * W]) {
-#pragma unroll
-    for (int i = 0; i < W; i++) {
-        const kv_half2 h = __builtin_bit_cast(kv_half2, w[i]);
-        f[2 * i] = (float)h[0]; f[2 * i + 1] = (float)h[1];
-    }
-}
-
 template <int HD, int R>
 __global__ __launch_bounds__(64 * kAsWaves) void attention_split_f16_kernel(const float* __restrict__ q, const _Float16* __restrict__ kCache,
                                                                             const _Float16* __restrict__ vCache, const uint32_t* __restrict__ posPtr,

@@ -199,15 +199,26 @@ class Decoder:
     effort_rope_kv_f16 + effort_attention_split_f16 (one captured step per effort, whatever ``fused_attention`` and the folded glue say)
     and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"`` only).  Any model kind; K and V are
     rounded to f16 on their way into the cache, nothing upstream of the rope changes.  Needs R in 1, 2, 4, 8 and headDim 64 / 128 / 256;
-    not with a column-sharded decoder, and not with ``split_attention_from`` (the split is implied)."""
+    not with a column-sharded decoder, and not with ``split_attention_from`` (the split is implied).
+
+    ``window``: None, the default -- every query attends from token 0 and every launch is as above.  An integer W (with
+    ``kv_cache="f16"`` only) -- sliding-window attention over ROLLING caches (csrc/kv_window.hip): the query at position p sees tokens
+    max(0, p + 1 - W) .. p, Mistral's ``sliding_window`` rule, and token t lives in row t % (W + 64) of a ring of W + 64 rows -- 64 more
+    than the window so that a prefill block of 64 tokens never overwrites a token its first query still sees.  A window no position can
+    outgrow masks nothing, so W counts as min(W, maxTokens): the caches have min(maxTokens, W) + 64 rows whatever the context, and
+    ``maxTokens`` bounds only the positions -- ``history``, ``seq`` -- and may go to 1048576.  The token step is effort_rope_kv_ring + effort_attention_window, whose
+    cost stops growing at position W - 1; ``prefill`` (``attention="block"``) runs effort_rope_kv_rows_ring +
+    effort_attention_block_window.  Any model kind.  Below position W the bits are the plain f16 decoder's.  Needs W + 64 <= 32768."""
 
     def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
                  world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False,
-                 split_attention_from: int | None = None, kv_cache: str = "f32"):
+                 split_attention_from: int | None = None, kv_cache: str = "f32", window: int | None = None):
         cfg = self.cfg = model.cfg
         if kv_cache not in ("f32", "f16"):
             raise ValueError(f"Decoder: kv_cache must be 'f32' or 'f16', not {kv_cache!r}")
         self.kv16 = kv_cache == "f16"
+        if window is not None and (not self.kv16 or int(window) < 1):
+            raise ValueError("Decoder: window needs kv_cache='f16' and window >= 1")
         if self.kv16 and split_attention_from is not None:
             raise ValueError("Decoder: kv_cache='f16' implies the split attention at every position; leave split_attention_from out")
         if self.kv16 and (sharded or emulate_world or int(world) > 1):
@@ -285,11 +296,17 @@ class Decoder:
             self.gateIdxs = torch.zeros(2, dtype=torch.int32, device=dev)
         self.logits = f(cfg.vocab)
         if self.kv16:
-            if (not 1 <= self.maxTokens <= 32768 or cfg.headDim not in (64, 128, 256) or cfg.numHeads % cfg.numHeadsKV
-                    or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8)):
-                raise ValueError("Decoder: kv_cache='f16' needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 32768")
-            cache = lambda: torch.zeros((self.maxTokens, cfg.numHeadsKV, cfg.headDim), dtype=torch.float16, device=dev)   # noqa: E731
+            # a window no position can outgrow masks nothing: min(window, maxTokens) is the same function and keeps the ring in range
+            self.window = None if window is None else min(int(window), self.maxTokens)
+            self.ringRows = None if window is None else self.window + 64
+            if (not 1 <= self.maxTokens <= (32768 if window is None else 1048576) or cfg.headDim not in (64, 128, 256)
+                    or cfg.numHeads % cfg.numHeadsKV or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8) or (self.ringRows or 0) > 32768):
+                raise ValueError("Decoder: kv_cache='f16' needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 32768 "
+                                 "(with a window: maxTokens <= 1048576, window + 64 <= 32768)")
+            cacheRows = self.maxTokens if window is None else self.ringRows
+            cache = lambda: torch.zeros((cacheRows, cfg.numHeadsKV, cfg.headDim), dtype=torch.float16, device=dev)   # noqa: E731
         else:
+            self.window = self.ringRows = None
             cache = lambda: f(self.maxTokens, cfg.numHeads, cfg.headDim)                                # noqa: E731
         self.kCache = [cache() for _ in range(cfg.numLayers)]                                           # xkLayerTokenHead
         self.vCache = [cache() for _ in range(cfg.numLayers)]                                           # xvLayerToken
@@ -312,7 +329,8 @@ class Decoder:
             self.splitScratch = f(nbytes // 4)
         if self.kv16:                                     # (the scratch as above: the f16 kernel leaves the same partial states)
             lib = _lib.lib()
-            splits = lib.effort_attention_split_default_splits(self.g.ctx, cfg.numHeadsKV, self.maxTokens)
+            splits = (lib.effort_attention_split_default_splits(self.g.ctx, cfg.numHeadsKV, self.maxTokens) if self.window is None else
+                      lib.effort_attention_window_default_splits(self.g.ctx, cfg.numHeadsKV, self.window))
             nbytes = lib.effort_attention_split_scratch_bytes(cfg.numHeads, cfg.headDim, splits) if splits >= 1 else 0
             if nbytes <= 0:
                 raise ValueError(f"Decoder: kv_cache='f16': the library resolved no split count for this shape (default splits {splits})")
@@ -423,7 +441,12 @@ class Decoder:
 
         def attention(n):                                  # xq_temp, xk_temp, xv_temp -> attnOutput, the caches at pos written
             kc, vc, rope = _p(self.kCache[n]), _p(self.vCache[n]), C.c_float(cfg.ropeBase)
-            if self.kv16:                                  # the compact f16 caches: one path at every position
+            if self.window is not None:                    # the rolling f16 caches: the windowed split attention at every position
+                ck(lib.effort_rope_kv_ring(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
+                                           cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.ringRows, self.maxTokens, rope), "rope_kv_ring")
+                ck(lib.effort_attention_window(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), _p(self.splitScratch),
+                                               cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.ringRows, self.window, 0), "attention_window")
+            elif self.kv16:                                # the compact f16 caches: one path at every position
                 ck(lib.effort_rope_kv_f16(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
                                           cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_f16")
                 ck(lib.effort_attention_split_f16(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), _p(self.splitScratch),
@@ -735,7 +758,11 @@ class Decoder:
         if self.kv16 and attention != "block":
             raise ValueError("Decoder.prefill: a kv_cache='f16' decoder prefills with attention='block' (there is no rows kernel for the f16 cache)")
         kvh = (cfg.numHeadsKV,) if self.kv16 else ()       # (the f16 entry points take the KV heads: the cache holds them alone)
-        if self.kv16:
+        cacheArgs, windowArgs = (self.maxTokens,), ()      # what follows headDim in the cache writer's and the attention's arguments
+        if self.window is not None:
+            rope_rows, attend, attendName = lib.effort_rope_kv_rows_ring, lib.effort_attention_block_window, "attention_block_window"
+            cacheArgs, windowArgs = (self.ringRows,), (self.window,)
+        elif self.kv16:
             rope_rows, attend, attendName = lib.effort_rope_kv_rows_f16, lib.effort_attention_block_f16, "attention_block_f16"
         else:
             rope_rows = lib.effort_rope_kv_rows
@@ -773,10 +800,10 @@ class Decoder:
                 for ew, out in ((L.wq, self.pf_xq_temp), (L.wk, self.pf_xk_temp), (L.wv, self.pf_xv_temp)):
                     mul(self.pf_norm, ew, out, rows)
                 ck(rope_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
-                             cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.maxTokens, rope), "rope_kv_rows")
+                             cfg.numHeads, cfg.numHeadsKV, cfg.headDim, *cacheArgs, rope), "rope_kv_rows")
                 if n == len(m.layers) - 1:
                     break                                  # nothing after the last layer's cache write reaches a cache
-                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, *kvh, cfg.headDim, self.maxTokens), attendName)
+                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, *kvh, cfg.headDim, *cacheArgs, *windowArgs), attendName)
                 mul(self.pf_attnOutput, L.wo, self.pf_attnFfnOut, rows)
                 ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
                 if routed:

@@ -363,6 +363,40 @@ EFFORT_API int effort_rope_kv_f16(effort_ctx* ctx, const float* xq_dev, const fl
 EFFORT_API int effort_attention_split_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev,
                                const uint32_t* pos_dev, float* out_dev, float* scratch_dev, int numHeads, int numHeadsKV, int headDim,
                                int maxTokens, int splits);
+/* ---- sliding-window attention over a ROLLING f16 KV cache (opt-in; nothing above reads or writes it) ----
+ * The compact format with a ring in place of the token axis: K and V each f16 [ringRows][numHeadsKV][headDim], token t in row
+ * t % ringRows, KV head g serving query heads g * R .. g * R + R - 1.  The query at position p sees tokens lo(p) .. p,
+ * lo(p) = max(0, p + 1 - window): `window` keys including its own (Mistral's sliding_window rule).  ringRows >= window serves token
+ * steps; a block of `rows` tokens needs ringRows >= window + rows - 1.  A step's attention then costs what it costs at position
+ * window - 1 at every later position, and positions run to 1048576 whatever ringRows is (they stay exact as f32 in the rope).
+ * Its entry points -- the three below, effort_rope_kv_rows_ring and effort_attention_block_window further down -- take headDim
+ * 64 / 128 / 256, R 1 / 2 / 4 / 8 and 1 <= window <= ringRows <= 32768; anything else returns EFFORT_ERR_SHAPE.  The argument VALUES are
+ * judged before the pointers (a null pointer: EFFORT_ERR_ARG), nothing is enqueued by a refusal.
+ *
+ * effort_rope_kv_ring: effort_rope_kv_f16 with the K / V slot at row *pos_dev % ringRows: q_out_dev and the stored halves are its bits
+ * (the f32 rope, one conversion, overflow to +-inf), each element written once, no other row touched.  A step at *pos_dev >= maxPos
+ * writes nothing and raises bit 0 of the decode status; 1 <= maxPos <= 1048576, ropeBase > 1, else EFFORT_ERR_SHAPE.
+ *
+ * effort_attention_window: out[h] = softmax(q[h] . K[t] / sqrt(headDim)) . V[t] over tokens t = lo(*pos_dev) .. *pos_dev, read from the
+ * ring.  effort_attention_split_f16's two launches, grid, scratch (effort_attention_split_scratch_bytes; holds no state between calls),
+ * merge and arithmetic (halves widened in registers, q in f32, f32 multiply-adds); capturable, the key range comes from *pos_dev on the
+ * device, so one captured call serves every position.  Key tiles stay on absolute multiples of 64 counted from token 0: the live ones
+ * are lo / 64 .. *pos_dev / 64, split s of S takes ceil(live tiles / S) consecutive ones.  A key outside the window is selected out
+ * (never multiplied by zero), and only ring rows of tokens inside the window are read: every other row may hold NaN.
+ *   splits 1 .. 64, or 0: effort_attention_window_default_splits(ctx, numHeadsKV, window) -- effort_attention_split_default_splits's rule
+ *   applied to window + 64 keys (the most tiles a window can touch).
+ * Bar: effort_attention_split_f16's, against the float64 attention over the halves the ring HOLDS.  The output's bits are a function
+ * of q, the tokens in the window, *pos_dev, window, the resolved splits and R; identical run to run.  At *pos_dev < window with
+ * ringRows > *pos_dev they are effort_attention_split_f16's bits at equal splits.
+ * Refusals in this order: the shape EFFORT_ERR_SHAPE; splits outside 0 .. 64 EFFORT_ERR_ARG; a null argument (scratch_dev included)
+ * EFFORT_ERR_ARG.  effort_attention_window_default_splits: EFFORT_ERR_ARG for a null ctx, numHeadsKV < 1 or window outside 1 .. 32768. */
+EFFORT_API int effort_rope_kv_ring(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
+                        void* k_ring_f16_dev, void* v_ring_f16_dev, const uint32_t* pos_dev, int numHeads, int numHeadsKV, int headDim,
+                        int ringRows, int maxPos, float ropeBase);
+EFFORT_API int effort_attention_window_default_splits(effort_ctx* ctx, int numHeadsKV, int window);
+EFFORT_API int effort_attention_window(effort_ctx* ctx, const float* q_dev, const void* k_ring_f16_dev, const void* v_ring_f16_dev,
+                            const uint32_t* pos_dev, float* out_dev, float* scratch_dev, int numHeads, int numHeadsKV, int headDim,
+                            int ringRows, int window, int splits);
 /* silu(x1, x3, out:) = x3 * x1 / (1 + exp(-x1)) (matrix.metal:25-35). */
 EFFORT_API int effort_silu_mul(effort_ctx* ctx, const float* x1_dev, const float* x3_dev, float* out_dev, int n);
 /* tokEmbeddings.fetchRow(id, out:) (aux.metal:355): row *id_dev of an f16 [vocab][n] table as f32. */
@@ -557,6 +591,23 @@ EFFORT_API int effort_rope_kv_rows_f16(effort_ctx* ctx, const float* xq_dev, con
                             int maxTokens, float ropeBase);
 EFFORT_API int effort_attention_block_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev, int pos0,
                                int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
+/* The block forms on the rolling cache (see effort_rope_kv_ring for the format and the shapes).
+ * effort_rope_kv_rows_ring: effort_rope_kv_rows_f16 with token pos0 + r in ring row (pos0 + r) % ringRows: per row its bits, q_out
+ *   included; those `rows` ring rows are written, no other.  rows <= ringRows.
+ * effort_attention_block_window: effort_attention_block_f16 over the ring with a per-query lower bound: query r sees tokens
+ *   lo(pos0 + r) .. pos0 + r.  A workgroup is one head and 16 queries and starts at key tile lo(its first query) / 16; key tiles stay on
+ *   absolute multiples of 16, the wave that owns a tile follows from its absolute index, a key a query may not see is selected out and a
+ *   tile wholly masked for a query leaves its state as it was, bit for bit.  So an output row's bits are a function of the query, its
+ *   absolute position, the window and the tokens in its window -- not of pos0, rows or the chunk -- and at pos0 + rows <= window they
+ *   are effort_attention_block_f16's.  Needs window + rows - 1 <= ringRows (the block's last write must not land on a token its first
+ *   query still sees).  Only ring rows of tokens lo(pos0) .. pos0 + rows - 1 are read; same bar as effort_attention_block_f16.
+ * Refusals in this order: rows outside 1 .. 64, pos0 < 0 EFFORT_ERR_ARG; the shape, pos0 + rows > 1048576 included, EFFORT_ERR_SHAPE;
+ * a null pointer EFFORT_ERR_ARG. */
+EFFORT_API int effort_rope_kv_rows_ring(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
+                             void* k_ring_f16_dev, void* v_ring_f16_dev, int pos0, int rows, int numHeads, int numHeadsKV, int headDim,
+                             int ringRows, float ropeBase);
+EFFORT_API int effort_attention_block_window(effort_ctx* ctx, const float* q_dev, const void* k_ring_f16_dev, const void* v_ring_f16_dev,
+                                  int pos0, int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int ringRows, int window);
 
 /* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */
 

@@ -95,6 +95,9 @@ EFFORT_API int effort_debug_lanes(int lanes, int nOps, const int64_t* ops, int64
  * 64-key tiles split `split` of `splits` owns when nTok cache rows are live (first == end: an empty split).  No context, no device, no HIP
  * call.  EFFORT_ERR_ARG for nTok < 1, splits outside 1 .. 64 or split outside 0 .. splits - 1. */
 EFFORT_API int effort_debug_attention_split_range(int nTok, int splits, int split, int* tiles2);
+/* The same for effort_attention_window (attention_window_tiles, the function its kernel calls): the absolute 64-key tiles split `split`
+ * of `splits` owns at position pos with `window` keys live.  EFFORT_ERR_ARG for pos < 0, window < 1 or the split arguments above. */
+EFFORT_API int effort_debug_attention_window_range(int pos, int window, int splits, int split, int* tiles2);
 /* enable = 3 (device clock + trace): every work item of the most recent multiply launch leaves a 64-byte record
  * {item | workgroup << 32 (bit 63: cutoff job), XCC_ID | HW_ID << 32, six device wall-clock stamps: start, staged,
  * cutoff, selected, streamed, handed over}; copies the first maxRecords (<= 4096) records to host (8 u64 each), followed

@@ -22,7 +22,9 @@ argmax_kernel and sample_kernel; its record also goes to profiles/r14_decode_rul
 decode loop from position 4000 and from 0 with and without `split_attention_from`; its record also goes to
 profiles/r15_attention_split.json; standalone too) and `decode_kv16` (the compact f16 KV cache beside the f32 one: effort_rope_kv +
 effort_attention_split against the _f16 pair by position, to 32767 for the f16 pair, and Mistral-7B-shaped decodes with
-split_attention_from=0 against kv_cache="f16" with the caches' memory; its record also goes to profiles/r16_kv16.json; standalone too).
+split_attention_from=0 against kv_cache="f16" with the caches' memory; its record also goes to profiles/r16_kv16.json; standalone too)
+and `decode_window` (sliding-window attention over the rolling f16 cache beside the plain f16 cache at positions 1023 .. 32767, and
+tokens/s from position 32000 with and without window=4096; its record also goes to profiles/r17_kv_window.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -40,8 +42,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1243,6 +1245,109 @@ def decode_kv16(b, res):
     del decs, model
 
 
+def decode_window(b, res):
+    """Sliding-window attention over the rolling f16 cache (csrc/kv_window.hip) beside the plain f16 cache, one process, the legs' windows
+    alternating.  Kernel legs, decode_kv16's protocol: 32 heads, 8 KV heads, headDim 128, eight ROTATING cache pairs per graph, device
+    events: effort_rope_kv_ring + effort_attention_window (window 4096, ring 4160 rows) against effort_rope_kv_f16 +
+    effort_attention_split_f16 (maxTokens 32768) at the same position, default splits, the comparator timed TWICE per position (its
+    run-to-run spread); one pair of block calls, 64 rows: effort_attention_block_window at position 8128 against
+    effort_attention_block_f16 at position 4032.  Model legs, Mistral-7B shapes, 25 % effort: tokens/s over 64 captured steps from
+    position 32000, kv_cache="f16" with window=4096 against without, and the cache bytes of each."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(89)
+    nh, nkv, hd, pairs, rope, window, maxTokens = 32, 8, 128, 8, C.c_float(1e6), 4096, 32768
+    ring = window + 64
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    plain = [(rnd(maxTokens, nkv, hd).half(), rnd(maxTokens, nkv, hd).half()) for _ in range(pairs)]
+    rings = [(rnd(ring, nkv, hd).half(), rnd(ring, nkv, hd).half()) for _ in range(pairs)]
+    xq, xk, xv, qr, out = rnd(nh * hd), rnd(nkv * hd), rnd(nkv * hd), rnd(nh * hd), torch.zeros(nh * hd, device=b.dev)
+    xq64, out64 = rnd(64, nh * hd), torch.zeros(64, nh * hd, device=b.dev)
+    scratch = torch.zeros(lib.effort_attention_split_scratch_bytes(nh, hd, 64) // 4, device=b.dev)
+    posd = torch.zeros(1, dtype=torch.int32, device=b.dev)
+
+    def step(windowed):
+        def fn():
+            g._bind_stream()
+            for kc, vc in (rings if windowed else plain):
+                if windowed:
+                    g.check(lib.effort_rope_kv_ring(g.ctx, p(xq), p(xk), p(xv), p(qr), p(kc), p(vc), p(posd), nh, nkv, hd, ring, 1 << 20, rope), "rope_kv_ring")
+                    g.check(lib.effort_attention_window(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), p(scratch), nh, nkv, hd, ring, window, 0), "attention_window")
+                else:
+                    g.check(lib.effort_rope_kv_f16(g.ctx, p(xq), p(xk), p(xv), p(qr), p(kc), p(vc), p(posd), nh, nkv, hd, maxTokens, rope), "rope_kv_f16")
+                    g.check(lib.effort_attention_split_f16(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), p(scratch), nh, nkv, hd, maxTokens, 0), "attention_split_f16")
+        return fn
+
+    def block(windowed, pos0):
+        def fn():
+            g._bind_stream()
+            for kc, vc in (rings if windowed else plain):
+                if windowed:
+                    g.check(lib.effort_attention_block_window(g.ctx, p(xq64), p(kc), p(vc), pos0, 64, p(out64), nh, nkv, hd, ring, window), "attention_block_window")
+                else:
+                    g.check(lib.effort_attention_block_f16(g.ctx, p(xq64), p(kc), p(vc), pos0, 64, p(out64), nh, nkv, hd, maxTokens), "attention_block_f16")
+        return fn
+    kern = {"protocol": "a step's attention (cache write, partial states, merge) on 8 rotating cache pairs per graph, 4 replays per window, best of 3 windows, "
+                        "device events, the legs' windows alternating; f16 and f16_again are the same comparator captured twice: their difference is the spread",
+            "heads": nh, "headsKV": nkv, "headDim": hd, "window": window, "ringRows": ring, "f16_maxTokens": maxTokens,
+            "splits": {"window": lib.effort_attention_window_default_splits(g.ctx, nkv, window), "f16": lib.effort_attention_split_default_splits(g.ctx, nkv, maxTokens)}}
+    for pos in (1023, 4095, 8191, 32767):
+        posd.fill_(pos)
+        us = alternating_us(b, {"window": step(True), "f16": step(False), "f16_again": step(False)}, pairs)
+        kern[f"pos_{pos}"] = dict({name + "_us_per_step": round(t, 2) for name, t in us.items()}, f16_over_window_time=round(us["f16"] / us["window"], 3))
+    us = alternating_us(b, {"window_at_8128": block(True, 8128), "f16_at_4032": block(False, 4032), "f16_at_4032_again": block(False, 4032)}, pairs)
+    kern["block_64_rows"] = {name + "_us_per_call": round(t, 2) for name, t in us.items()}
+    del plain, rings
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "effort": 0.25, "maxTokens": maxTokens, "window": window,
+         "protocol": "each Decoder's step graph captured on empty (zero) caches -- the kernels' time does not depend on the values; per leg the position is "
+                     "set to 32000, 4 warm replays, the position set again, 64 replays between synchronised wall-clock reads, best of 2; the f16 leg runs "
+                     "twice, around the windowed one"}
+    decs = {}
+    for name, how in (("f16", {}), ("window", dict(window=window))):
+        dec = Decoder(model, maxTokens=maxTokens, kv_cache="f16", **how)
+        m[f"{name}_cache_bytes"] = int(sum(c.numel() * c.element_size() for c in dec.kCache + dec.vCache))
+        gr = dec._graph(0.25, False)
+        B._GRAPHS_FOR_LIFE.extend(dec._graphs.values())
+        decs[name] = (dec, gr)
+    for name in ("f16", "window", "f16"):
+        dec, gr = decs[name]
+        best = float("inf")
+        for _ in range(2):
+            for steps in (4, 64):
+                dec.pos.fill_(32000)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    gr.replay()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+            best = min(best, dt)
+        key = f"from_32000_{name}_tokens_per_s"
+        m[key + "_again" if key in m else key] = round(64 / best, 1)
+    m["from_32000_window_over_f16"] = round(m["from_32000_window_tokens_per_s"] / m["from_32000_f16_tokens_per_s"], 3)
+    m["decode_status"] = [dec.status() for dec, _ in decs.values()]
+    res_out["model"] = m
+    res["decode_window"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r17_kv_window.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del decs, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1260,7 +1365,8 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "shard_projection": shard_projection, "decode_quality": decode_quality, "layer_latency": layer_latency, "decode_q4": decode_q4,
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
-       "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16}
+       "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
+       "decode_window": decode_window}
 
 
 class Light:

@@ -295,6 +295,12 @@ hipError_t launch_attention_split_f16(const float* q, const _Float16* kCache, co
                                       uint32_t splits, hipStream_t st);
 hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
                                       uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
+// ... and its one-launch token step for short contexts (kv16_short.hip): rope, the write of row *pos and the attention over rows
+// 0 .. *pos < maxKeys, one workgroup per query head, the scores in maxKeys floats of dynamic LDS
+constexpr int kShortMaxKeys = 2048;
+hipError_t launch_rope_attention_f16(const float* xq, const float* xk, const float* xv, _Float16* kCache, _Float16* vCache, const uint32_t* pos,
+                                     float* out, uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t maxKeys, float ropeBase,
+                                     int* status, hipStream_t st);
 
 // the rolling f16 cache [ringRows][numHeadsKV][headDim], token t in row t % ringRows, with sliding-window attention over it
 // (kv_window.hip): the writers, the windowed split decode attention (launch_attention_split's scratch and merge) and block attention

@@ -163,6 +163,17 @@ extern "C" int effort_rope_kv_f16(effort_ctx* c, const float* xq, const float* x
     return HIP_RC(c, launch_rope_kv_f16(xq, xk, xv, qOut, static_cast<_Float16*>(kCache), static_cast<_Float16*>(vCache), pos, (uint32_t)numHeads,
                                         (uint32_t)numHeadsKV, (uint32_t)headDim, ropeBase, (uint32_t)maxTokens, c->d_status + 1, c->stream));
 }
+// (kv16_short.hip: one launch; the plain cache or the ring below its window, cacheRows rows either way)
+extern "C" int effort_rope_attention_f16(effort_ctx* c, const float* xq, const float* xk, const float* xv, void* kCache, void* vCache,
+                                         const uint32_t* pos, float* out, int numHeads, int numHeadsKV, int headDim, int cacheRows, int maxKeys,
+                                         float ropeBase) {
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, cacheRows) || maxKeys < 1 || maxKeys > cacheRows || maxKeys > kShortMaxKeys || !(ropeBase > 1.0f))
+        return kv16_refuse(c, "rope_attention_f16", EFFORT_ERR_SHAPE, "headDim 64/128/256, heads per KV head 1/2/4/8, cacheRows <= 32768, 1 <= maxKeys <= min(cacheRows, 2048)");
+    if (!c || !xq || !xk || !xv || !kCache || !vCache || !pos || !out) return kv16_refuse(c, "rope_attention_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_rope_attention_f16(xq, xk, xv, static_cast<_Float16*>(kCache), static_cast<_Float16*>(vCache), pos, out, (uint32_t)numHeads,
+                                               (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)maxKeys, ropeBase, c->d_status + 1, c->stream));
+}
 extern "C" int effort_attention_split_f16(effort_ctx* c, const float* q, const void* kCache, const void* vCache, const uint32_t* pos, float* out,
                                           float* scratch, int numHeads, int numHeadsKV, int headDim, int maxTokens, int splits) {
     if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens)) return kv16_refuse(c, "attention_split_f16", EFFORT_ERR_SHAPE, kKv16Shape);

@@ -208,17 +208,29 @@ class Decoder:
     outgrow masks nothing, so W counts as min(W, maxTokens): the caches have min(maxTokens, W) + 64 rows whatever the context, and
     ``maxTokens`` bounds only the positions -- ``history``, ``seq`` -- and may go to 1048576.  The token step is effort_rope_kv_ring + effort_attention_window, whose
     cost stops growing at position W - 1; ``prefill`` (``attention="block"``) runs effort_rope_kv_rows_ring +
-    effort_attention_block_window.  Any model kind.  Below position W the bits are the plain f16 decoder's.  Needs W + 64 <= 32768."""
+    effort_attention_block_window.  Any model kind.  Below position W the bits are the plain f16 decoder's.  Needs W + 64 <= 32768.
+
+    ``short_attention_below``: None, the default -- every launch is as above.  An integer P (with ``kv_cache="f16"`` only, with or without
+    ``window``) -- ``run`` takes every step at a position < P through a second captured step (``token_step(short=True)``) whose attention
+    is ONE launch per layer, effort_rope_attention_f16 (csrc/kv16_short.hip: rope, the cache write and the attention over tokens
+    0 .. pos, one workgroup per query head), in place of the two calls above; from P on the step above.  Same caches, the same bits
+    written into the same rows; the short step's logits are within the f32 bar of the split step's, NOT its bits (another order of the
+    sums).  Needs 1 <= P <= min(2048, maxTokens, W if a window is given).  Recommended P: 1024 -- measured at 32 / 8 heads of
+    headDim 128, the one launch is ahead of the two-call path at every position to 1023 (4.96 against 17.6 us per step's attention at
+    position 63, 19.3 against 22.2 at 1023) and behind at 2047 (35.0 against 25.7): DESIGN 4.4e."""
 
     def __init__(self, model: Model, maxTokens: int = 256, fused_attention: bool = True, fused_glue=None,
                  world: int = 1, rank: int = 0, sharded: bool | None = None, emulate_world: bool = False,
-                 split_attention_from: int | None = None, kv_cache: str = "f32", window: int | None = None):
+                 split_attention_from: int | None = None, kv_cache: str = "f32", window: int | None = None,
+                 short_attention_below: int | None = None):
         cfg = self.cfg = model.cfg
         if kv_cache not in ("f32", "f16"):
             raise ValueError(f"Decoder: kv_cache must be 'f32' or 'f16', not {kv_cache!r}")
         self.kv16 = kv_cache == "f16"
         if window is not None and (not self.kv16 or int(window) < 1):
             raise ValueError("Decoder: window needs kv_cache='f16' and window >= 1")
+        if short_attention_below is not None and not self.kv16:
+            raise ValueError("Decoder: short_attention_below needs kv_cache='f16'")
         if self.kv16 and split_attention_from is not None:
             raise ValueError("Decoder: kv_cache='f16' implies the split attention at every position; leave split_attention_from out")
         if self.kv16 and (sharded or emulate_world or int(world) > 1):
@@ -303,10 +315,10 @@ class Decoder:
                     or cfg.numHeads % cfg.numHeadsKV or cfg.numHeads // cfg.numHeadsKV not in (1, 2, 4, 8) or (self.ringRows or 0) > 32768):
                 raise ValueError("Decoder: kv_cache='f16' needs numHeads / numHeadsKV in 1, 2, 4, 8, headDim 64 / 128 / 256, maxTokens <= 32768 "
                                  "(with a window: maxTokens <= 1048576, window + 64 <= 32768)")
-            cacheRows = self.maxTokens if window is None else self.ringRows
+            cacheRows = self.cacheRows = self.maxTokens if window is None else self.ringRows
             cache = lambda: torch.zeros((cacheRows, cfg.numHeadsKV, cfg.headDim), dtype=torch.float16, device=dev)   # noqa: E731
         else:
-            self.window = self.ringRows = None
+            self.window = self.ringRows = self.cacheRows = None
             cache = lambda: f(self.maxTokens, cfg.numHeads, cfg.headDim)                                # noqa: E731
         self.kCache = [cache() for _ in range(cfg.numLayers)]                                           # xkLayerTokenHead
         self.vCache = [cache() for _ in range(cfg.numLayers)]                                           # xvLayerToken
@@ -335,6 +347,9 @@ class Decoder:
             if nbytes <= 0:
                 raise ValueError(f"Decoder: kv_cache='f16': the library resolved no split count for this shape (default splits {splits})")
             self.splitScratch = f(nbytes // 4)
+        self.short_attention_below = None if short_attention_below is None else int(short_attention_below)
+        if self.short_attention_below is not None and not 1 <= self.short_attention_below <= min(2048, self.maxTokens, self.window or self.maxTokens):
+            raise ValueError("Decoder: short_attention_below needs 1 <= P <= min(2048, maxTokens, window)")
         self.dense_expert_gemv = None                     # Mixtral dense baseline: whether its last step went through effort_dense_gemv_expert (else: gathered cores)
         self._pf = None                                   # prefill's block buffers: made by the first ``prefill`` (see ``_prefill_buffers``)
         self.last_prefill_s = None                        # run(prefill=True): synchronised wall time of its prefill
@@ -342,7 +357,7 @@ class Decoder:
         self.stopped_at = None                            # run(rules=...): the step that picked a stop token, or None
 
     # -- one token: everything between fetching the embedding and picking the next token ----------------------------
-    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None, rules=None, split: bool = False):
+    def token_step(self, effort: float = 0.25, dense: bool = False, sampling=None, rules=None, split: bool = False, short: bool = False):
         """ONE walk serves every model and every setting: the embedding fetch; per layer an attention half (norm -> wq | wk | wv ->
         rope + cache + attention -> wo -> residual) and an FFN half (norm -> w1 | w3 -> silu -> w2 -> residual, or with an ffnGate the
         routed form: gate + top-2 -> both experts' w1 | w3 as one group of four -> both w2 as one group of two -> mix); then the closing
@@ -376,12 +391,17 @@ class Decoder:
         -- the same on what the device tensors hold (the captured form).
 
         ``split``: every layer's attention is effort_rope_kv + effort_attention_split (three launches: the cache write, the partial
-        states, their merge) whatever ``fused_attention`` and the folded glue say; a Decoder made with ``split_attention_from``."""
+        states, their merge) whatever ``fused_attention`` and the folded glue say; a Decoder made with ``split_attention_from``.
+
+        ``short``: every layer's attention is ONE call, effort_rope_attention_f16 on the f16 caches (plain or rolling) with maxKeys =
+        ``short_attention_below``, in place of the f16 path's two; a Decoder made with ``short_attention_below``, positions below it."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         if split and self.kv16:
             raise ValueError("Decoder.token_step(split=True): a kv_cache='f16' decoder's only step is already the split one; leave split out")
         if split and self.splitScratch is None:
             raise ValueError("Decoder.token_step(split=True): make the Decoder with split_attention_from")
+        if short and self.short_attention_below is None:
+            raise ValueError("Decoder.token_step(short=True): make the Decoder with short_attention_below")
         g._bind_stream()
         sampled = sampling is not None and sampling is not False
         if isinstance(sampling, Sampling):
@@ -441,7 +461,11 @@ class Decoder:
 
         def attention(n):                                  # xq_temp, xk_temp, xv_temp -> attnOutput, the caches at pos written
             kc, vc, rope = _p(self.kCache[n]), _p(self.vCache[n]), C.c_float(cfg.ropeBase)
-            if self.window is not None:                    # the rolling f16 caches: the windowed split attention at every position
+            if short:                                      # the f16 caches, plain or rolling, below short_attention_below: one launch
+                ck(lib.effort_rope_attention_f16(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), kc, vc, _p(self.pos),
+                                                 _p(self.attnOutput), cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.cacheRows,
+                                                 self.short_attention_below, rope), "rope_attention_f16")
+            elif self.window is not None:                  # the rolling f16 caches: the windowed split attention at every position
                 ck(lib.effort_rope_kv_ring(g.ctx, _p(self.xq_temp), _p(self.xk_temp), _p(self.xv_temp), _p(self.xq), kc, vc, _p(self.pos),
                                            cfg.numHeads, cfg.numHeadsKV, cfg.headDim, self.ringRows, self.maxTokens, rope), "rope_kv_ring")
                 ck(lib.effort_attention_window(g.ctx, _p(self.xq), kc, vc, _p(self.pos), _p(self.attnOutput), _p(self.splitScratch),
@@ -824,7 +848,7 @@ class Decoder:
                 delta = self.pf_ffnOut
         self.pos.fill_(pos0 + T)
 
-    def _graph(self, effort: float, dense: bool, sampled: bool = False, ruled: bool = False, split: bool = False):
+    def _graph(self, effort: float, dense: bool, sampled: bool = False, ruled: bool = False, split: bool = False, short: bool = False):
         key = ("dense",) if dense else (float(effort),)
         if sampled:                                              # the ONLY thing sampling adds to the key: its settings are device values
             key += ("sampled",)
@@ -832,8 +856,10 @@ class Decoder:
             key += ("rules",)
         if split:                                                # ... and the split attention: the step of the positions >= split_attention_from
             key += ("split",)
+        if short:                                                # ... or the one-launch f16 attention: the step of the positions < short_attention_below
+            key += ("short",)
         pick, rules = True if sampled else None, True if ruled else None
-        step = (effort, dense, pick, rules) + ((True,) if split else ())         # (without the option: today's call)
+        step = (effort, dense, pick, rules) + ((True,) if split else (False, True) if short else ())     # (without an option: today's call)
         if key not in self._graphs:
             self.reset()
             self.token_step(*step)                               # warm (handles, kernel attributes, rocBLAS, the rules' buffers)
@@ -886,6 +912,7 @@ class Decoder:
         None), and ``pos`` / ``tokId`` are set to continue behind it -- what the replays past it wrote is junk that the next steps
         overwrite.  With ``forced`` the window is the forced inputs and nothing stops.
         With ``split_attention_from`` = P the steps at positions >= P replay the split-attention graph, the others the ordinary one.
+        With ``short_attention_below`` = P the steps at positions < P replay the short-attention graph, the others the ordinary one.
         Returns (token ids picked at every step, seconds per step measured from the 3rd step on like the reference,
         logits per step if asked)."""
         assert 1 <= len(tokenIds) and numTokens <= self.maxTokens
@@ -898,6 +925,8 @@ class Decoder:
         gr = self._graph(effort, dense, sampling is not None, *((True,) if rules is not None else ()))    # (a run without rules: today's call)
         splitFrom = self.split_attention_from                    # (both graphs BEFORE the reset: _graph resets the position)
         grSplit = None if splitFrom is None else self._graph(effort, dense, sampling is not None, rules is not None, split=True)
+        shortBelow = self.short_attention_below
+        grShort = None if shortBelow is None else self._graph(effort, dense, sampling is not None, rules is not None, short=True)
         self.reset()
         if sampling is not None:
             self.set_sampling(sampling)
@@ -925,7 +954,10 @@ class Decoder:
             if step == max(2, skip):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-            (gr if grSplit is None or step < splitFrom else grSplit).replay()    # (the host's step counter is the position)
+            if grShort is not None and step < shortBelow:        # (the host's step counter is the position)
+                grShort.replay()
+            else:
+                (gr if grSplit is None or step < splitFrom else grSplit).replay()
             if collect_logits:
                 logits.append(self.logits.clone())
             if step >= 2:

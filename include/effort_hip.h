@@ -339,7 +339,7 @@ EFFORT_API int effort_attention_split(effort_ctx* ctx, const float* q_dev, const
                            int maxTokens, int splits);
 /* ---- the compact f16 KV cache (opt-in; nothing above reads or writes it) ----
  * K and V each f16 [maxTokens][numHeadsKV][headDim], row t = token t, KV head g serving query heads g * R .. g * R + R - 1,
- * R = numHeads / numHeadsKV: 1 / (2 R) of the f32 cache's memory.  Its entry points -- the two below, effort_rope_kv_rows_f16 and
+ * R = numHeads / numHeadsKV: 1 / (2 R) of the f32 cache's memory.  Its entry points -- the three below, effort_rope_kv_rows_f16 and
  * effort_attention_block_f16 further down -- take maxTokens 1 .. 32768, headDim 64 / 128 / 256 and R 1 / 2 / 4 / 8; anything else returns
  * EFFORT_ERR_SHAPE.  The argument VALUES are judged before the pointers (a null pointer: EFFORT_ERR_ARG), nothing is enqueued by a refusal.
  *
@@ -356,7 +356,22 @@ EFFORT_API int effort_attention_split(effort_ctx* ctx, const float* q_dev, const
  * in DESIGN 4.4c).  No cache row past *pos_dev is read.  The output's bits are a function of q, cache rows 0 .. *pos_dev, *pos_dev, the
  * resolved splits and R; they are identical run to run.  A V element stored as +-inf makes the outputs it reaches non-finite (inf or NaN).
  * Refusals in this order: the shape EFFORT_ERR_SHAPE; splits outside 0 .. 64
- * EFFORT_ERR_ARG; a null argument (scratch_dev included) EFFORT_ERR_ARG. */
+ * EFFORT_ERR_ARG; a null argument (scratch_dev included) EFFORT_ERR_ARG.
+ *
+ * effort_rope_attention_f16: the two calls above as ONE launch, for short contexts -- effort_rope_attention on this format.  It ropes
+ * xq and xk at *pos_dev, writes row *pos_dev of both caches (effort_rope_kv_f16's bits, each element once, no other row) and attends
+ * tokens 0 .. *pos_dev: out[h] = softmax(q[h] . K[t] / sqrt(headDim)) . V[t], the newest token taken as the halves just stored.  One
+ * workgroup per query head, the scores in maxKeys floats of LDS; capturable, one captured call serves every position below maxKeys.
+ * The caches have cacheRows rows (the shapes above on cacheRows) and 1 <= maxKeys <= min(cacheRows, 2048); ropeBase > 1; anything else
+ * returns EFFORT_ERR_SHAPE, then a null argument EFFORT_ERR_ARG.  A step at *pos_dev >= maxKeys writes nothing, caches and out_dev
+ * alike, and raises bit 0 of the decode status.  It serves the rolling cache of the next block too while *pos_dev < window and
+ * *pos_dev < ringRows (cacheRows = ringRows): token t is row t there and nothing is masked.  Bar: effort_attention_split_f16's,
+ * against the float64 attention over the halves the caches hold AFTER the call; the output is within that bar of what
+ * effort_attention_split_f16 computes from the same caches, not its bits (another order of the sums); its bits are a function of the
+ * inputs, rows 0 .. *pos_dev - 1, *pos_dev and R, identical run to run.  A stored +-inf makes the outputs it reaches non-finite. */
+EFFORT_API int effort_rope_attention_f16(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev,
+                              void* k_cache_f16_dev, void* v_cache_f16_dev, const uint32_t* pos_dev, float* out_dev,
+                              int numHeads, int numHeadsKV, int headDim, int cacheRows, int maxKeys, float ropeBase);
 EFFORT_API int effort_rope_kv_f16(effort_ctx* ctx, const float* xq_dev, const float* xk_dev, const float* xv_dev, float* q_out_dev,
                        void* k_cache_f16_dev, void* v_cache_f16_dev, const uint32_t* pos_dev, int numHeads, int numHeadsKV, int headDim,
                        int maxTokens, float ropeBase);

@@ -24,7 +24,10 @@ profiles/r15_attention_split.json; standalone too) and `decode_kv16` (the compac
 effort_attention_split against the _f16 pair by position, to 32767 for the f16 pair, and Mistral-7B-shaped decodes with
 split_attention_from=0 against kv_cache="f16" with the caches' memory; its record also goes to profiles/r16_kv16.json; standalone too)
 and `decode_window` (sliding-window attention over the rolling f16 cache beside the plain f16 cache at positions 1023 .. 32767, and
-tokens/s from position 32000 with and without window=4096; its record also goes to profiles/r17_kv_window.json; standalone too).
+tokens/s from position 32000 with and without window=4096; its record also goes to profiles/r17_kv_window.json; standalone too) and
+`decode_kv16_short` (the one-launch token attention over the f16 cache, effort_rope_attention_f16, beside effort_rope_attention on f32
+caches and the f16 split pair at positions 15 .. 2047, and tokens/s from position 0 with and without short_attention_below; its record
+also goes to profiles/r18_kv16_short.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -42,8 +45,8 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short")           # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1348,6 +1351,102 @@ def decode_window(b, res):
     del decs, model
 
 
+def decode_kv16_short(b, res):
+    """The one-launch token attention over the f16 cache (csrc/kv16_short.hip) beside what it stands in for and what it aims at, one
+    process, the legs' windows alternating.  Kernel legs, decode_kv16's protocol: 32 heads, 8 KV heads, headDim 128, eight steps per
+    graph on ROTATING cache pairs (eight f16, four f32 walked twice), device events: effort_rope_attention on f32 caches (the target),
+    effort_rope_kv_f16 + effort_attention_split_f16 timed TWICE (its spread is the noise floor), effort_rope_attention_f16 (maxKeys
+    2048), all on caches of 2048 rows.  Model legs, Mistral-7B shapes, 25 % effort, 64 captured steps from position 0: kv_cache f32, f16,
+    f16 with short_attention_below=2048 (the cap: every measured step is a short one), f16 again."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(97)
+    nh, nkv, hd, pairs, rows, rope = 32, 8, 128, 4, 2048, C.c_float(1e6)
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    c32 = [(rnd(rows, nh, hd), rnd(rows, nh, hd)) for _ in range(pairs)]
+    c16 = [(rnd(rows, nkv, hd).half(), rnd(rows, nkv, hd).half()) for _ in range(2 * pairs)]
+    xq, xk, xv, qr, out = rnd(nh * hd), rnd(nkv * hd), rnd(nkv * hd), rnd(nh * hd), torch.zeros(nh * hd, device=b.dev)
+    scratch = torch.zeros(lib.effort_attention_split_scratch_bytes(nh, hd, 64) // 4, device=b.dev)
+    posd = torch.zeros(1, dtype=torch.int32, device=b.dev)
+
+    def leg(kind):
+        def fn():
+            g._bind_stream()
+            for kc, vc in (c32 + c32 if kind == "f32_one_launch" else c16):      # eight steps per graph either way
+                if kind == "f32_one_launch":
+                    g.check(lib.effort_rope_attention(g.ctx, p(xq), p(xk), p(xv), p(kc), p(vc), p(posd), p(out), nh, nkv, hd, rows, rope), kind)
+                elif kind == "f16_one_launch":
+                    g.check(lib.effort_rope_attention_f16(g.ctx, p(xq), p(xk), p(xv), p(kc), p(vc), p(posd), p(out), nh, nkv, hd, rows, rows, rope), kind)
+                else:
+                    g.check(lib.effort_rope_kv_f16(g.ctx, p(xq), p(xk), p(xv), p(qr), p(kc), p(vc), p(posd), nh, nkv, hd, rows, rope), "rope_kv_f16")
+                    g.check(lib.effort_attention_split_f16(g.ctx, p(qr), p(kc), p(vc), p(posd), p(out), p(scratch), nh, nkv, hd, rows, 0), "attention_split_f16")
+        return fn
+    legs = {"f32_one_launch": leg("f32_one_launch"), "f16_split": leg("f16_split"), "f16_one_launch": leg("f16_one_launch"), "f16_split_again": leg("f16_split")}
+    kern = {"protocol": "a step's attention on rotating cache pairs of 2048 rows, 4 of f32 walked twice / 8 of f16, eight steps per graph, 4 replays per "
+                        "window, best of 3 windows, device events, the legs' windows alternating; f16_split and f16_split_again are the same leg "
+                        "captured twice: their difference is the spread",
+            "heads": nh, "headsKV": nkv, "headDim": hd, "cacheRows": rows, "maxKeys": rows,
+            "splits": lib.effort_attention_split_default_splits(g.ctx, nkv, rows)}
+    for pos in (15, 63, 255, 511, 1023, 2047):
+        posd.fill_(pos)
+        us = {name: t / (2 * pairs) for name, t in alternating_us(b, legs, 1).items()}
+        kern[f"pos_{pos}"] = dict({name + "_us_per_step": round(t, 2) for name, t in us.items()},
+                                  split_over_one_launch_time=round(us["f16_split"] / us["f16_one_launch"], 3),
+                                  f32_over_f16_one_launch_time=round(us["f32_one_launch"] / us["f16_one_launch"], 3))
+        B.log(f"decode_kv16_short: pos {pos}: {kern[f'pos_{pos}']}")
+    del c32, c16
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    below = 2048                                                                 # the cap: all 64 measured steps are short ones whatever P is recommended later
+    model = Model.random(MistralConfig(), seed=1)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "effort": 0.25, "maxTokens": 4096, "short_attention_below": below,
+         "protocol": "each Decoder's step graph captured on empty (zero) caches; per leg the position is set to 0, 4 warm replays, the position set "
+                     "again, 64 replays between synchronised wall-clock reads, best of 2; the f16 leg runs twice, around the short one, which "
+                     "replays the short step of a Decoder made with short_attention_below"}
+    decs = {}
+    for name, how in (("f32", {}), ("f16", dict(kv_cache="f16")), ("f16_short", dict(kv_cache="f16", short_attention_below=below))):
+        dec = Decoder(model, maxTokens=4096, **how)
+        gr = dec._graph(0.25, False, short=name == "f16_short")
+        B._GRAPHS_FOR_LIFE.extend(dec._graphs.values())
+        decs[name] = (dec, gr)
+        B.log(f"decode_kv16_short: {name} decoder captured")
+    for name in ("f32", "f16", "f16_short", "f16"):
+        dec, gr = decs[name]
+        best = float("inf")
+        for _ in range(2):
+            for steps in (4, 64):
+                dec.pos.fill_(0)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    gr.replay()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+            best = min(best, dt)
+        key = f"from_0_{name}_tokens_per_s"
+        m[key + "_again" if key in m else key] = round(64 / best, 1)
+    m["from_0_f16_short_over_f16"] = round(m["from_0_f16_short_tokens_per_s"] / m["from_0_f16_tokens_per_s"], 3)
+    m["from_0_f16_short_over_f32"] = round(m["from_0_f16_short_tokens_per_s"] / m["from_0_f32_tokens_per_s"], 3)
+    m["decode_status"] = [dec.status() for dec, _ in decs.values()]
+    res_out["model"] = m
+    res["decode_kv16_short"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r18_kv16_short.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del decs, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1366,7 +1465,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
        "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
-       "decode_window": decode_window}
+       "decode_window": decode_window, "decode_kv16_short": decode_kv16_short}
 
 
 class Light:

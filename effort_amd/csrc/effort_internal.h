@@ -295,6 +295,10 @@ hipError_t launch_attention_split_f16(const float* q, const _Float16* kCache, co
                                       uint32_t splits, hipStream_t st);
 hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
                                       uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
+// ... the same block of queries with both products on the f16 matrix instruction, q and the probabilities split into two halves
+// (attention_flash16.hip: 32-key tiles, V transposed through LDS; the f32 bar, other bits)
+hipError_t launch_attention_flash_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                      uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
 // ... and its one-launch token step for short contexts (kv16_short.hip): rope, the write of row *pos and the attention over rows
 // 0 .. *pos < maxKeys, one workgroup per query head, the scores in maxKeys floats of dynamic LDS
 constexpr int kShortMaxKeys = 2048;

@@ -197,7 +197,7 @@ class Decoder:
     it serves, and everything above applies.  ``"f16"`` -- the compact caches, torch.float16 [maxTokens][numHeadsKV][headDim] (csrc/kv16.hip):
     1 / (2 R) of the memory, R = numHeads / numHeadsKV, and maxTokens up to 32768.  EVERY token step's attention is then
     effort_rope_kv_f16 + effort_attention_split_f16 (one captured step per effort, whatever ``fused_attention`` and the folded glue say)
-    and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"`` only).  Any model kind; K and V are
+    and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"``; ``"flash"``: effort_attention_flash_f16).  Any model kind; K and V are
     rounded to f16 on their way into the cache, nothing upstream of the rope changes.  Needs R in 1, 2, 4, 8 and headDim 64 / 128 / 256;
     not with a column-sharded decoder, and not with ``split_attention_from`` (the split is implied).
 
@@ -707,8 +707,10 @@ class Decoder:
         ``attention``: ``"rows"`` is effort_attention_rows (every query of a block reads its keys and values again; the token step's
         bits); ``"block"`` puts effort_attention_block in its place, same operands -- the block's queries share each K / V tile, f32
         MFMA with an online softmax, within the f32 bar of the same float64 value but not the same bits.  On either path the caches
-        do not depend on ``chunk``.  A ``kv_cache="f16"`` decoder has no rows kernel: it takes ``"block"`` alone, through
-        effort_rope_kv_rows_f16 + effort_attention_block_f16.
+        do not depend on ``chunk``.  A ``kv_cache="f16"`` decoder has no rows kernel: it takes ``"block"``, through
+        effort_rope_kv_rows_f16 + effort_attention_block_f16, or -- without a ``window`` -- ``"flash"``, which puts
+        effort_attention_flash_f16 in the attention's place: both products on the f16 MFMA, q and the probabilities split into two
+        halves each, the same f32 bar, other bits, the caches again independent of ``chunk``.  Opt-in: nothing selects it by default.
 
         ``ffn``: ``"dense"``, the default, is the walk above and serves dense-FFN models only.  ``"routed"`` serves a Mixtral model (FP16,
         an ffnGate in every layer, numExperts >= 2, the expert stacks' cores [E, out, in] kept): the second half of a layer becomes
@@ -738,8 +740,8 @@ class Decoder:
         un-bucketable and ``ffn="routed"``; under ``"buckets"`` a Q4
         or core-only bundle, a bundle truncated below ``percentLoad`` 16 and one that is not un-bucketable; a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
-        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"``, an ``ffn`` other
-        than ``"dense"`` / ``"routed"``."""
+        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"``,
+        ``"flash"`` on an f32-cache or a ``window`` decoder, an ``ffn`` other than ``"dense"`` / ``"routed"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
         T = len(ids)
@@ -777,9 +779,12 @@ class Decoder:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
-        if attention not in ("rows", "block"):
-            raise ValueError(f"Decoder.prefill: attention must be 'rows' or 'block', not {attention!r}")
-        if self.kv16 and attention != "block":
+        if attention not in ("rows", "block", "flash"):
+            raise ValueError(f"Decoder.prefill: attention must be 'rows', 'block' or 'flash', not {attention!r}")
+        if attention == "flash" and (not self.kv16 or self.window is not None):
+            raise ValueError("Decoder.prefill: attention must be " + ("'block'" if self.kv16 else "'rows' or 'block'") + " on this decoder: 'flash' is "
+                             "for kv_cache='f16' without a window (effort_attention_flash_f16 reads the compact f16 cache; there is no ring form)")
+        if self.kv16 and attention == "rows":
             raise ValueError("Decoder.prefill: a kv_cache='f16' decoder prefills with attention='block' (there is no rows kernel for the f16 cache)")
         kvh = (cfg.numHeadsKV,) if self.kv16 else ()       # (the f16 entry points take the KV heads: the cache holds them alone)
         cacheArgs, windowArgs = (self.maxTokens,), ()      # what follows headDim in the cache writer's and the attention's arguments
@@ -787,7 +792,9 @@ class Decoder:
             rope_rows, attend, attendName = lib.effort_rope_kv_rows_ring, lib.effort_attention_block_window, "attention_block_window"
             cacheArgs, windowArgs = (self.ringRows,), (self.window,)
         elif self.kv16:
-            rope_rows, attend, attendName = lib.effort_rope_kv_rows_f16, lib.effort_attention_block_f16, "attention_block_f16"
+            rope_rows = lib.effort_rope_kv_rows_f16
+            attend, attendName = ((lib.effort_attention_flash_f16, "attention_flash_f16") if attention == "flash" else
+                                  (lib.effort_attention_block_f16, "attention_block_f16"))
         else:
             rope_rows = lib.effort_rope_kv_rows
             attend, attendName = ((lib.effort_attention_rows, "attention_rows") if attention == "rows" else
@@ -899,7 +906,7 @@ class Decoder:
         and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
-        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
+        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"``),``prefill_ffn`` its ``ffn`` (``"dense"`` /
         ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
         FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
         and the caches then hold effort-1.0 K / V, not dense ones).

@@ -606,6 +606,16 @@ EFFORT_API int effort_rope_kv_rows_f16(effort_ctx* ctx, const float* xq_dev, con
                             int maxTokens, float ropeBase);
 EFFORT_API int effort_attention_block_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev, int pos0,
                                int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
+/* effort_attention_flash_f16: effort_attention_block_f16's operands, refusals and guarantees with both products on the f16 matrix
+ *   instruction (v_mfma_f32_16x16x32_f16).  q and the probabilities are each split into two halves, hi = f16(x), lo = f16(x - hi),
+ *   after an exact power-of-two pre-scale (per query row for q, 2^14 for the probabilities), and every product is issued once per
+ *   part: the cache's halves are exact operands, the sums are f32, and the result meets the SAME bar as effort_attention_block_f16
+ *   against float64 over the f16 values the cache holds.  Key tiles are 32 keys on absolute multiples of 32, V is transposed through
+ *   LDS.  An output row's bits are a function of the query, its absolute position pos0 + r and cache rows 0 .. pos0 + r -- not of pos0,
+ *   rows or r on their own; they are NOT effort_attention_block_f16's bits (another order of the sums).  No cache row at or past
+ *   pos0 + rows and no q row at or past rows is read; nothing outside out[0 .. rows) is written. */
+EFFORT_API int effort_attention_flash_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev, int pos0,
+                               int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
 /* The block forms on the rolling cache (see effort_rope_kv_ring for the format and the shapes).
  * effort_rope_kv_rows_ring: effort_rope_kv_rows_f16 with token pos0 + r in ring row (pos0 + r) % ringRows: per row its bits, q_out
  *   included; those `rows` ring rows are written, no other.  rows <= ringRows.

@@ -27,7 +27,9 @@ and `decode_window` (sliding-window attention over the rolling f16 cache beside 
 tokens/s from position 32000 with and without window=4096; its record also goes to profiles/r17_kv_window.json; standalone too) and
 `decode_kv16_short` (the one-launch token attention over the f16 cache, effort_rope_attention_f16, beside effort_rope_attention on f32
 caches and the f16 split pair at positions 15 .. 2047, and tokens/s from position 0 with and without short_attention_below; its record
-also goes to profiles/r18_kv16_short.json; standalone too).
+also goes to profiles/r18_kv16_short.json; standalone too) and `prefill_attention_flash` (the block attention over the f16 cache on the
+f16 MFMA, effort_attention_flash_f16, beside effort_attention_block_f16 at positions 0 .. 32704, and `Decoder.prefill` over 2048 tokens
+both ways; its record also goes to profiles/r19_attention_flash16.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -45,8 +47,10 @@ import bench as B  # noqa: E402
 
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
-            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short")
-STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short")           # sections that read neither the headline nor the matrix sets of bench.Bench
+            "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
+            "prefill_attention_flash")
+STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
+              "prefill_attention_flash")   # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1447,6 +1451,71 @@ def decode_kv16_short(b, res):
     del decs, model
 
 
+def prefill_attention_flash(b, res):
+    """Prefill attention over the compact f16 cache: effort_attention_block_f16 (f32 MFMA on widened halves) beside
+    effort_attention_flash_f16 (f16 MFMA, q and the probabilities split in two), one process, the legs' windows alternating.  Kernel
+    legs, decode_kv16's protocol: 32 heads, 8 KV heads, headDim 128, maxTokens 32768, eight ROTATING cache pairs per graph, device
+    events; the block kernel is captured TWICE (its run-to-run spread).  Model legs, Mistral-7B shapes: `Decoder.prefill` over a
+    2048-token prompt at chunk 64 on a kv_cache="f16" decoder, block / flash / block again; ms per prompt token."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(101)
+    nh, nkv, hd, pairs, maxTokens = 32, 8, 128, 8, 32768
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    caches = [(rnd(maxTokens, nkv, hd).half(), rnd(maxTokens, nkv, hd).half()) for _ in range(pairs)]
+    q, outs = rnd(64, nh * hd), {name: torch.zeros(64, nh * hd, device=b.dev) for name in ("block", "flash")}
+
+    def leg(name, pos0, rows):
+        entry = lib.effort_attention_flash_f16 if name == "flash" else lib.effort_attention_block_f16
+
+        def fn():
+            g._bind_stream()
+            for kc, vc in caches:
+                g.check(entry(g.ctx, p(q), p(kc), p(vc), pos0, rows, p(outs[name]), nh, nkv, hd, maxTokens), "attention_" + name + "_f16")
+        return fn
+    kern = {"protocol": "one pass over 8 rotating f16 cache pairs per graph, 4 replays per window, best of 3 windows, device events, the legs' windows "
+                        "alternating; block and block_again are the same comparator captured twice: their difference is the spread; "
+                        "flash_error_over_block_max is max|flash - block| / max|block| of the last pair's 64 x 4096 outputs",
+            "heads": nh, "headsKV": nkv, "headDim": hd, "maxTokens": maxTokens}
+    for pos0, rows in ((0, 64), (960, 64), (4032, 64), (8128, 64), (32704, 64), (4032, 16)):
+        us = alternating_us(b, {"block": leg("block", pos0, rows), "flash": leg("flash", pos0, rows), "block_again": leg("block", pos0, rows)}, pairs)
+        torch.cuda.synchronize()
+        err = float((outs["flash"][:rows] - outs["block"][:rows]).abs().max() / outs["block"][:rows].abs().max())
+        kern[f"pos0_{pos0}_rows_{rows}"] = dict({name + "_us_per_call": round(t, 2) for name, t in us.items()},
+                                                block_over_flash_time=round(us["block"] / us["flash"], 3), flash_error_over_block_max=err)
+        B.log(f"prefill_attention_flash: pos0 {pos0} rows {rows}: {kern[f'pos0_{pos0}_rows_{rows}']}")
+    del caches, q, outs
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    nprompt = 2048
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "chunk": 64, "kv_cache": "f16", "prompt": nprompt,
+         "protocol": "eager, synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call; block twice, around flash"}
+    dec = Decoder(model, maxTokens=nprompt + 8, kv_cache="f16")
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+    for attention in ("block", "flash", "block"):
+        key = f"{attention}_ms_per_prompt_token"
+        m[key + "_again" if key in m else key] = timed_prefill(b, dec, prompt, chunk=64, attention=attention)
+    m["block_over_flash"] = round(m["block_ms_per_prompt_token"] / m["flash_ms_per_prompt_token"], 3)
+    res_out["model"] = m
+    res["prefill_attention_flash"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r19_attention_flash16.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1465,7 +1534,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
        "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
-       "decode_window": decode_window, "decode_kv16_short": decode_kv16_short}
+       "decode_window": decode_window, "decode_kv16_short": decode_kv16_short, "prefill_attention_flash": prefill_attention_flash}
 
 
 class Light:

@@ -93,6 +93,7 @@ _SIGS = {
     "effort_debug_attention_window_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "effort_rope_kv_rows_ring": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "effort_attention_block_window": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "effort_attention_flash_window": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "effort_silu_mul": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "effort_fetch_row": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "effort_argmax": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int]),

@@ -320,6 +320,11 @@ hipError_t launch_attention_window(const float* q, const _Float16* kRing, const 
 hipError_t launch_attention_block_window(const float* q, const _Float16* kRing, const _Float16* vRing, uint32_t pos0, uint32_t rows, float* out,
                                          uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t ringRows, uint32_t window,
                                          hipStream_t st);
+// ... the same block over the ring with both products on the f16 matrix instruction (attention_flash_window.hip:
+// launch_attention_flash_f16's arithmetic with the window's walk, mask and ring rows; its bits while pos0 + rows <= window)
+hipError_t launch_attention_flash_window(const float* q, const _Float16* kRing, const _Float16* vRing, uint32_t pos0, uint32_t rows, float* out,
+                                         uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, uint32_t ringRows, uint32_t window,
+                                         hipStream_t st);
 
 // the sampled pick (sample.hip)
 hipError_t launch_sample(const float* logits, uint32_t n, const void* params, uint32_t* idOut, uint32_t* pos, uint32_t* history, uint32_t historyLen,

@@ -496,6 +496,16 @@ extern "C" int effort_attention_block_window(effort_ctx* c, const float* q, cons
     return HIP_RC(c, launch_attention_block_window(q, static_cast<const _Float16*>(kRing), static_cast<const _Float16*>(vRing), (uint32_t)pos0, (uint32_t)rows, out,
                                                    (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)ringRows, (uint32_t)window, c->stream));
 }
+extern "C" int effort_attention_flash_window(effort_ctx* c, const float* q, const void* kRing, const void* vRing, int pos0, int rows, float* out,
+                                             int numHeads, int numHeadsKV, int headDim, int ringRows, int window) {
+    if (!prefill_rows_ok(rows) || pos0 < 0) return kv16_refuse(c, "attention_flash_window", EFFORT_ERR_ARG, "1 <= rows <= 64, 0 <= pos0");
+    if (!kv_window_shape_ok(numHeads, numHeadsKV, headDim, ringRows, window, rows) || pos0 > kWindowMaxPos - rows)
+        return kv16_refuse(c, "attention_flash_window", EFFORT_ERR_SHAPE, kWindowShape);
+    if (!c || !q || !kRing || !vRing || !out) return kv16_refuse(c, "attention_flash_window", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_attention_flash_window(q, static_cast<const _Float16*>(kRing), static_cast<const _Float16*>(vRing), (uint32_t)pos0, (uint32_t)rows, out,
+                                                   (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, (uint32_t)ringRows, (uint32_t)window, c->stream));
+}
 extern "C" int effort_top2_softmax(effort_ctx* c, const float* gate, int n, uint32_t* idx2, float* val2) {
     if (!c || !gate || !idx2 || !val2 || n < 1) return fail(c, EFFORT_ERR_ARG, "top2_softmax: bad argument");
     JOIN_TRY(c);

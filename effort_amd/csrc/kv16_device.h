@@ -33,6 +33,21 @@ __device__ __forceinline__ void rope_kv_f16_row(const float* __restrict__ xq, co
     vCache[slot] = (_Float16)xv[g * headDim + d];
 }
 
+// The ring rows of one key tile (kv_window.hip, attention_flash_window.hip): `first` is the tile's first live key, row0 its row (both
+// uniform in the wave).
+struct ring_tile {
+    uint32_t first, last, row0, ringRows;
+    // the row of `key` clamped into first .. last; last - first < ringRows
+    __device__ __forceinline__ uint32_t row(uint32_t key) const {
+        const uint32_t r = row0 + (min(max(key, first), last) - first);
+        return r >= ringRows ? r - ringRows : r;
+    }
+};
+__device__ __forceinline__ ring_tile ring_tile_at(uint32_t key0, uint32_t lo, uint32_t last, uint32_t ringRows) {
+    const uint32_t first = max(key0, lo);
+    return ring_tile{first, last, (uint32_t)__builtin_amdgcn_readfirstlane(first % ringRows), ringRows};   // the ONE division of a tile
+}
+
 typedef _Float16 kv_half2 __attribute__((ext_vector_type(2)));
 
 // W 32-bit words (2 W halves) of a cache row in one load: 16 bytes (W = 4) or 8 (W = 2)

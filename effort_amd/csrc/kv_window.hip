@@ -57,21 +57,7 @@ __global__ void rope_kv_rows_ring_kernel(const float* __restrict__ xq, const flo
                     logBase);
 }
 
-// ---- the windowed split decode attention
-// The ring rows of one key tile: `first` is the tile's first live key, row0 its row (both uniform in the wave).
-struct ring_tile {
-    uint32_t first, last, row0, ringRows;
-    // the row of `key` clamped into first .. last; last - first < ringRows
-    __device__ __forceinline__ uint32_t row(uint32_t key) const {
-        const uint32_t r = row0 + (min(max(key, first), last) - first);
-        return r >= ringRows ? r - ringRows : r;
-    }
-};
-__device__ __forceinline__ ring_tile ring_tile_at(uint32_t key0, uint32_t lo, uint32_t last, uint32_t ringRows) {
-    const uint32_t first = max(key0, lo);
-    return ring_tile{first, last, (uint32_t)__builtin_amdgcn_readfirstlane(first % ringRows), ringRows};   // the ONE division of a tile
-}
-
+// ---- the windowed split decode attention (the ring rows of a key tile: ring_tile, kv16_device.h)
 template <int HD, int R>
 __global__ __launch_bounds__(64 * kAsWaves) void attention_window_kernel(const float* __restrict__ q, const _Float16* __restrict__ kRing,
                                                                          const _Float16* __restrict__ vRing, const uint32_t* __restrict__ posPtr,

@@ -208,7 +208,7 @@ class Decoder:
     outgrow masks nothing, so W counts as min(W, maxTokens): the caches have min(maxTokens, W) + 64 rows whatever the context, and
     ``maxTokens`` bounds only the positions -- ``history``, ``seq`` -- and may go to 1048576.  The token step is effort_rope_kv_ring + effort_attention_window, whose
     cost stops growing at position W - 1; ``prefill`` (``attention="block"``) runs effort_rope_kv_rows_ring +
-    effort_attention_block_window.  Any model kind.  Below position W the bits are the plain f16 decoder's.  Needs W + 64 <= 32768.
+    effort_attention_block_window (``"flash_window"``: effort_attention_flash_window, the f16-MFMA form over the ring).  Any model kind.  Below position W the bits are the plain f16 decoder's.  Needs W + 64 <= 32768.
 
     ``short_attention_below``: None, the default -- every launch is as above.  An integer P (with ``kv_cache="f16"`` only, with or without
     ``window``) -- ``run`` takes every step at a position < P through a second captured step (``token_step(short=True)``) whose attention
@@ -711,6 +711,10 @@ class Decoder:
         effort_rope_kv_rows_f16 + effort_attention_block_f16, or -- without a ``window`` -- ``"flash"``, which puts
         effort_attention_flash_f16 in the attention's place: both products on the f16 MFMA, q and the probabilities split into two
         halves each, the same f32 bar, other bits, the caches again independent of ``chunk``.  Opt-in: nothing selects it by default.
+        A ``kv_cache="f16", window=W`` decoder takes ``"block"`` (effort_attention_block_window) or ``"flash_window"``, the ring form of
+        ``"flash"``: effort_attention_flash_window in the attention's place, same writer, same arguments; its bits are ``"flash"``'s
+        while the block ends at or below position W, and the rings do not depend on ``chunk``.  Opt-in as well; ``"flash"`` itself stays
+        refused on a window decoder.
 
         ``ffn``: ``"dense"``, the default, is the walk above and serves dense-FFN models only.  ``"routed"`` serves a Mixtral model (FP16,
         an ffnGate in every layer, numExperts >= 2, the expert stacks' cores [E, out, in] kept): the second half of a layer becomes
@@ -740,8 +744,9 @@ class Decoder:
         un-bucketable and ``ffn="routed"``; under ``"buckets"`` a Q4
         or core-only bundle, a bundle truncated below ``percentLoad`` 16 and one that is not un-bucketable; a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
-        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"``,
-        ``"flash"`` on an f32-cache or a ``window`` decoder, an ``ffn`` other than ``"dense"`` / ``"routed"``."""
+        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"`` /
+        ``"flash_window"``, ``"flash"`` on an f32-cache or a ``window`` decoder, ``"flash_window"`` on any decoder but a
+        ``kv_cache="f16", window=W`` one, an ``ffn`` other than ``"dense"`` / ``"routed"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
         T = len(ids)
@@ -779,17 +784,22 @@ class Decoder:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
-        if attention not in ("rows", "block", "flash"):
-            raise ValueError(f"Decoder.prefill: attention must be 'rows', 'block' or 'flash', not {attention!r}")
+        if attention not in ("rows", "block", "flash", "flash_window"):
+            raise ValueError(f"Decoder.prefill: attention must be 'rows', 'block', 'flash' or 'flash_window', not {attention!r}")
         if attention == "flash" and (not self.kv16 or self.window is not None):
             raise ValueError("Decoder.prefill: attention must be " + ("'block'" if self.kv16 else "'rows' or 'block'") + " on this decoder: 'flash' is "
-                             "for kv_cache='f16' without a window (effort_attention_flash_f16 reads the compact f16 cache; there is no ring form)")
+                             "for kv_cache='f16' without a window (effort_attention_flash_f16 reads the compact f16 cache; its ring form is 'flash_window')")
+        if attention == "flash_window" and self.window is None:
+            raise ValueError("Decoder.prefill: attention must be " + ("'block' or 'flash'" if self.kv16 else "'rows' or 'block'") + " on this decoder: "
+                             "'flash_window' is for kv_cache='f16' with a window (effort_attention_flash_window reads the rolling f16 cache)")
         if self.kv16 and attention == "rows":
             raise ValueError("Decoder.prefill: a kv_cache='f16' decoder prefills with attention='block' (there is no rows kernel for the f16 cache)")
         kvh = (cfg.numHeadsKV,) if self.kv16 else ()       # (the f16 entry points take the KV heads: the cache holds them alone)
         cacheArgs, windowArgs = (self.maxTokens,), ()      # what follows headDim in the cache writer's and the attention's arguments
         if self.window is not None:
-            rope_rows, attend, attendName = lib.effort_rope_kv_rows_ring, lib.effort_attention_block_window, "attention_block_window"
+            rope_rows = lib.effort_rope_kv_rows_ring
+            attend, attendName = ((lib.effort_attention_flash_window, "attention_flash_window") if attention == "flash_window" else
+                                  (lib.effort_attention_block_window, "attention_block_window"))
             cacheArgs, windowArgs = (self.ringRows,), (self.window,)
         elif self.kv16:
             rope_rows = lib.effort_rope_kv_rows_f16
@@ -906,7 +916,7 @@ class Decoder:
         and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
-        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"``),``prefill_ffn`` its ``ffn`` (``"dense"`` /
+        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"`` / ``"flash_window"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
         ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
         FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
         and the caches then hold effort-1.0 K / V, not dense ones).

@@ -384,7 +384,7 @@ EFFORT_API int effort_attention_split_f16(effort_ctx* ctx, const float* q_dev, c
  * lo(p) = max(0, p + 1 - window): `window` keys including its own (Mistral's sliding_window rule).  ringRows >= window serves token
  * steps; a block of `rows` tokens needs ringRows >= window + rows - 1.  A step's attention then costs what it costs at position
  * window - 1 at every later position, and positions run to 1048576 whatever ringRows is (they stay exact as f32 in the rope).
- * Its entry points -- the three below, effort_rope_kv_rows_ring and effort_attention_block_window further down -- take headDim
+ * Its entry points -- the three below, effort_rope_kv_rows_ring and effort_attention_block_window / _flash_window further down -- take headDim
  * 64 / 128 / 256, R 1 / 2 / 4 / 8 and 1 <= window <= ringRows <= 32768; anything else returns EFFORT_ERR_SHAPE.  The argument VALUES are
  * judged before the pointers (a null pointer: EFFORT_ERR_ARG), nothing is enqueued by a refusal.
  *
@@ -632,6 +632,21 @@ EFFORT_API int effort_rope_kv_rows_ring(effort_ctx* ctx, const float* xq_dev, co
                              void* k_ring_f16_dev, void* v_ring_f16_dev, int pos0, int rows, int numHeads, int numHeadsKV, int headDim,
                              int ringRows, float ropeBase);
 EFFORT_API int effort_attention_block_window(effort_ctx* ctx, const float* q_dev, const void* k_ring_f16_dev, const void* v_ring_f16_dev,
+                                  int pos0, int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int ringRows, int window);
+/* effort_attention_flash_window: effort_attention_block_window's operands, semantics, reads and refusals with
+ *   effort_attention_flash_f16's arithmetic: both products on v_mfma_f32_16x16x32_f16, q and the probabilities split hi / lo after
+ *   their power-of-two pre-scales, K and V exact operands, f32 sums, V transposed through LDS; the same bar.  Key tiles are 32 keys on
+ *   absolute multiples of 32, tile t on wave t % 4; a workgroup (one head, 16 queries) starts at tile lo(its first query) / 32, so past
+ *   the window it walks about (window + 16) / 32 tiles at every position.  ringRows need not be a multiple of 32: a tile the ring's
+ *   wrap cuts through maps each of its keys to its row.  Guarantees:
+ *   - while pos0 + rows <= window an output row has the BITS of effort_attention_flash_f16 for the same q and the same K / V on a
+ *     plain cache;
+ *   - at every position an output row's bits are a function of the query, its absolute position, window and the ring's contents for
+ *     its window -- not of pos0, rows, the row's place in the block or ringRows (a key a query may not see is selected out, a tile
+ *     wholly masked for a query leaves its state bit for bit); they are NOT effort_attention_block_window's bits;
+ *   - only ring rows of tokens lo(pos0) .. pos0 + rows - 1 and q rows below rows are read (the others may hold NaN); nothing outside
+ *     out[0 .. rows) is written. */
+EFFORT_API int effort_attention_flash_window(effort_ctx* ctx, const float* q_dev, const void* k_ring_f16_dev, const void* v_ring_f16_dev,
                                   int pos0, int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int ringRows, int window);
 
 /* ---- sampled pick: top-k / top-p / temperature on the device ------------------------------------ */

@@ -29,7 +29,10 @@ tokens/s from position 32000 with and without window=4096; its record also goes 
 caches and the f16 split pair at positions 15 .. 2047, and tokens/s from position 0 with and without short_attention_below; its record
 also goes to profiles/r18_kv16_short.json; standalone too) and `prefill_attention_flash` (the block attention over the f16 cache on the
 f16 MFMA, effort_attention_flash_f16, beside effort_attention_block_f16 at positions 0 .. 32704, and `Decoder.prefill` over 2048 tokens
-both ways; its record also goes to profiles/r19_attention_flash16.json; standalone too).
+both ways; its record also goes to profiles/r19_attention_flash16.json; standalone too) and `prefill_attention_flash_window` (its
+ring form, effort_attention_flash_window, beside effort_attention_block_window at window 4096 and positions 960 .. 32704, with
+effort_attention_flash_f16 over the same 4096 keys as the yardstick, and `Decoder.prefill` over 2048 tokens on a window=4096 decoder
+both ways; its record also goes to profiles/r20_attention_flash_window.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -48,9 +51,9 @@ import bench as B  # noqa: E402
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
             "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-            "prefill_attention_flash")
+            "prefill_attention_flash", "prefill_attention_flash_window")
 STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-              "prefill_attention_flash")   # sections that read neither the headline nor the matrix sets of bench.Bench
+              "prefill_attention_flash", "prefill_attention_flash_window")   # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1516,6 +1519,83 @@ def prefill_attention_flash(b, res):
     del dec, model
 
 
+def prefill_attention_flash_window(b, res):
+    """Prefill attention over the ROLLING f16 cache with a window: effort_attention_block_window (f32 MFMA on widened halves) beside
+    effort_attention_flash_window (f16 MFMA, q and the probabilities split in two), one process, the legs' windows alternating.  Kernel
+    legs, decode_window's protocol: 32 heads, 8 KV heads, headDim 128, window 4096, ring 4160 rows, eight ROTATING ring pairs per graph,
+    device events; the block kernel is captured TWICE (its run-to-run spread).  At position 4032 effort_attention_flash_f16 walks a plain
+    cache's same 4096 keys in the same alternation: the yardstick.  Model legs, Mistral-7B shapes: `Decoder.prefill` over a 2048-token
+    prompt at chunk 64 on a kv_cache="f16", window=4096 decoder, block / flash_window / block again; ms per prompt token."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(103)
+    nh, nkv, hd, pairs, window, plainTokens = 32, 8, 128, 8, 4096, 4096
+    ring = window + 64
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    rings = [(rnd(ring, nkv, hd).half(), rnd(ring, nkv, hd).half()) for _ in range(pairs)]
+    plain = [(rnd(plainTokens, nkv, hd).half(), rnd(plainTokens, nkv, hd).half()) for _ in range(pairs)]
+    q, outs = rnd(64, nh * hd), {name: torch.zeros(64, nh * hd, device=b.dev) for name in ("block", "flash_window", "flash_f16")}
+
+    def leg(name, pos0, rows):
+        def fn():
+            g._bind_stream()
+            for kc, vc in (plain if name == "flash_f16" else rings):
+                if name == "flash_f16":
+                    g.check(lib.effort_attention_flash_f16(g.ctx, p(q), p(kc), p(vc), pos0, rows, p(outs[name]), nh, nkv, hd, plainTokens), "attention_flash_f16")
+                else:
+                    entry = lib.effort_attention_flash_window if name == "flash_window" else lib.effort_attention_block_window
+                    g.check(entry(g.ctx, p(q), p(kc), p(vc), pos0, rows, p(outs[name]), nh, nkv, hd, ring, window), "attention_" + name)
+        return fn
+    kern = {"protocol": "one pass over 8 rotating f16 ring pairs per graph, 4 replays per window, best of 3 windows, device events, the legs' windows "
+                        "alternating; block and block_again are the same comparator captured twice: their difference is the spread; "
+                        "flash_window_error_over_block_max is max|flash_window - block| / max|block| of the last pair's outputs; flash_f16 at "
+                        "position 4032 is effort_attention_flash_f16 on plain caches of 4096 rows",
+            "heads": nh, "headsKV": nkv, "headDim": hd, "window": window, "ringRows": ring}
+    for pos0, rows in ((960, 64), (4032, 64), (8128, 64), (32704, 64), (8128, 16)):
+        legs = {"block": leg("block", pos0, rows), "flash_window": leg("flash_window", pos0, rows), "block_again": leg("block", pos0, rows)}
+        if pos0 == 4032:
+            legs["flash_f16"] = leg("flash_f16", pos0, rows)
+        us = alternating_us(b, legs, pairs)
+        torch.cuda.synchronize()
+        err = float((outs["flash_window"][:rows] - outs["block"][:rows]).abs().max() / outs["block"][:rows].abs().max())
+        rec = dict({name + "_us_per_call": round(t, 2) for name, t in us.items()}, block_over_flash_window_time=round(us["block"] / us["flash_window"], 3),
+                   flash_window_error_over_block_max=err)
+        if "flash_f16" in us:
+            rec["flash_window_over_flash_f16_time"] = round(us["flash_window"] / us["flash_f16"], 3)
+        kern[f"pos0_{pos0}_rows_{rows}"] = rec
+        B.log(f"prefill_attention_flash_window: pos0 {pos0} rows {rows}: {rec}")
+    del rings, plain, q, outs
+    torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    nprompt = 2048
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "chunk": 64, "kv_cache": "f16", "window": window, "prompt": nprompt,
+         "protocol": "eager, synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call; block twice, around flash_window"}
+    dec = Decoder(model, maxTokens=nprompt + 8, kv_cache="f16", window=window)
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+    for attention in ("block", "flash_window", "block"):
+        key = f"{attention}_ms_per_prompt_token"
+        m[key + "_again" if key in m else key] = timed_prefill(b, dec, prompt, chunk=64, attention=attention)
+    m["block_over_flash_window"] = round(m["block_ms_per_prompt_token"] / m["flash_window_ms_per_prompt_token"], 3)
+    res_out["model"] = m
+    res["prefill_attention_flash_window"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r20_attention_flash_window.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1534,7 +1614,8 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "decode_mixtral": decode_mixtral, "decode_sampled": decode_sampled, "decode_prefill": decode_prefill, "prefill_attention": prefill_attention,
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
        "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
-       "decode_window": decode_window, "decode_kv16_short": decode_kv16_short, "prefill_attention_flash": prefill_attention_flash}
+       "decode_window": decode_window, "decode_kv16_short": decode_kv16_short, "prefill_attention_flash": prefill_attention_flash,
+       "prefill_attention_flash_window": prefill_attention_flash_window}
 
 
 class Light:

@@ -112,6 +112,7 @@ _SIGS = {
     "effort_dense_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int]),
     "effort_dense_gemv_expert": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "effort_dense_gemm_rows": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "effort_dense_gemm_rows_wide": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "effort_dense_gemm_rows_routed": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "effort_weights_bucket_dense_ok": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "effort_bucket_gemm_rows": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),

@@ -262,6 +262,22 @@ extern "C" int effort_dense_gemm_rows(effort_ctx* c, const void* W, const float*
     return HIP_RC(c, launch_dense_gemm_rows(static_cast<const uint16_t*>(W), x, c->d_xhRows.buf, c->d_gemmPart.buf, out, (uint32_t)inDim, (uint32_t)outDim,
                                       (uint32_t)rows, c->stream));
 }
+// The wide block multiply (prefill_wide.hip): the same refusals in the same order, up to 256 rows, scratch of its own grown to 256 rows' worth
+// by the first call -- a context that never comes here allocates none of it.
+static_assert(EFFORT_PREFILL_WIDE_MAX_ROWS == kPrefillWideMaxRows, "prefill_wide.hip: two token groups of eight token tiles");
+extern "C" int effort_dense_gemm_rows_wide(effort_ctx* c, const void* W, const float* x, float* out, int inDim, int outDim, int rows) {
+    if (inDim <= 0 || outDim <= 0 || rows < 1 || rows > EFFORT_PREFILL_WIDE_MAX_ROWS)
+        return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows_wide: inDim, outDim >= 1, 1 <= rows <= 256");
+    if (!dense_gemm_rows_supported((uint32_t)inDim, (uint32_t)outDim))
+        return fail(c, EFFORT_ERR_SHAPE, "dense_gemm_rows_wide: inDim % 32 == 0, inDim <= 65536, outDim <= 2^24, W below 4 GiB");
+    if (!c || !W || !x || !out) return fail(c, EFFORT_ERR_ARG, "dense_gemm_rows_wide: null argument");
+    JOIN_TRY(c);
+    OK_TRY(c->d_xhWide.grow(c, (size_t)rows * inDim, (size_t)EFFORT_PREFILL_WIDE_MAX_ROWS * inDim));
+    OK_TRY(c->d_widePart.grow(c, dense_gemm_rows_wide_partial_floats((uint32_t)inDim, (uint32_t)outDim, (uint32_t)rows),
+                              dense_gemm_rows_wide_partial_floats((uint32_t)inDim, (uint32_t)outDim, EFFORT_PREFILL_WIDE_MAX_ROWS)));
+    return HIP_RC(c, launch_dense_gemm_rows_wide(static_cast<const uint16_t*>(W), x, c->d_xhWide.buf, c->d_widePart.buf, out, (uint32_t)inDim,
+                                                 (uint32_t)outDim, (uint32_t)rows, c->stream));
+}
 extern "C" int effort_dense_gemm_rows_routed(effort_ctx* c, const void* W, int numExperts, const uint32_t* idx2, const float* x, int xPerSlot, float* out,
                                              int inDim, int outDim, int rows) {
     if (inDim <= 0 || outDim <= 0 || numExperts <= 0 || !prefill_rows_ok(rows) || (xPerSlot != 0 && xPerSlot != 1))

@@ -51,7 +51,8 @@ struct Scratch {
     X(uint16_t, d_vhalf)        /* v.asFloat16() for the dense baseline */                                                                 \
     X(uint16_t, d_xhRows)       /* effort_dense_gemm_rows: f16(x) of a block.  Not d_vhalf: its address sits in captured token steps (rocBLAS backend) */ \
     X(float, d_gemmPart)        /* effort_dense_gemm_rows: the k splits' partial sums */                                                   \
-    X(uint16_t, d_xhRouted)     /* effort_dense_gemm_rows_routed: its OWN three (a captured effort_dense_gemm_rows keeps the block multiply's addresses) */ \
+    X(uint16_t, d_xhWide) X(float, d_widePart)      /* effort_dense_gemm_rows_wide: its OWN two, for the same reason as the routed call's */ \
+    X(uint16_t, d_xhRouted)    /* effort_dense_gemm_rows_routed: its OWN three (a captured effort_dense_gemm_rows keeps the block multiply's addresses) */ \
     X(float, d_routedPart) X(uint32_t, d_routedGroups)      /* ... the groups: per-expert counts and assignment lists (a fixed size) */    \
     X(uint16_t, d_convVals)     /* converter scratch (transposed matrix) */
 

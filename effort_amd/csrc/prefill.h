@@ -2,7 +2,8 @@
 // un-bucketed on the fly) and prefill_q4.hip (the Q4 buckets, de-quantised on the fly).  All walk K in stages of kPfStage under the
 // SAME k split and reduce it with the same kernel, so that a bucket kernel's bits are the core kernel's on the un-bucketed matrix.
 // The sequence of launches around the multiply is written here once (pf_block_call); a launcher hands it the launch of its own
-// kernel.  Read by glue.hip and the three prefill units alone.
+// kernel.  prefill_wide.hip (the f16 cores again, up to 256 rows) shares the split, the stage and the two kernels around the multiply.
+// Read by glue.hip and the four prefill units alone.
 #pragma once
 #include <type_traits>
 
@@ -98,6 +99,13 @@ size_t dense_gemm_rows_routed_group_words();                                    
 hipError_t launch_dense_gemm_rows_routed(const uint16_t* W_f16, uint32_t numExperts, const uint32_t* idx2, const float* x, uint32_t xPerSlot,
                                          uint16_t* xhScratch /* (xPerSlot ? 2 : 1) * rows * inDim halves */, float* partScratch, uint32_t* groupScratch,
                                          float* out, uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
+
+// prefill_wide.hip: the block multiply on the f16 cores for 1 .. kPrefillWideMaxRows rows, a tiling of its own (a wave on 2 W tiles x up to
+// 8 token tiles); per row the bits of launch_dense_gemm_rows.  The shapes are dense_gemm_rows_supported's.
+constexpr int kPrefillWideMaxRows = 256;  // == EFFORT_PREFILL_WIDE_MAX_ROWS (glue.hip asserts it)
+size_t dense_gemm_rows_wide_partial_floats(uint32_t inDim, uint32_t outDim, uint32_t rows);
+hipError_t launch_dense_gemm_rows_wide(const uint16_t* W_f16, const float* x, uint16_t* xhScratch /* rows * inDim halves */, float* partScratch, float* out,
+                                       uint32_t inDim, uint32_t outDim, uint32_t rows, hipStream_t st);
 
 // prefill_buckets.hip: the block multiply on the bucketed weights (FP16, percentLoad 16), un-bucketed on the fly; the scratch is the core
 // launchers', same sizes.  B is ONE expert's buckets for the plain launcher and the whole stack's for the routed one.

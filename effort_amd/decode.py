@@ -615,6 +615,7 @@ class Decoder:
 
     # -- prompt prefill: a block of tokens per pass over the weights ---------------------------------------------------
     PREFILL_MAX_ROWS = 64                                  # EFFORT_PREFILL_MAX_ROWS
+    PREFILL_WIDE_MAX_ROWS = 256                            # EFFORT_PREFILL_WIDE_MAX_ROWS
 
     def _prefill_buffers(self, chunk: int):
         """The block buffers of ``prefill`` ([chunk, stateDim], [chunk, hiddenDim] and the rest), made on first use and again only for a
@@ -639,7 +640,7 @@ class Decoder:
             self.pf_gateOut = torch.zeros((cfg.numLayers, chunk, cfg.numExperts), dtype=torch.float32, device=dev)
         self._pf = chunk
 
-    def _block_multiplies(self, from_buckets: bool, q4: bool = False):
+    def _block_multiplies(self, from_buckets: bool, q4: bool = False, wide: bool = False):
         """The two block multiplies of a ``prefill`` walk, chosen once per call by ``weights``:
 
         ``mul(x, ew, out, rows)``: out[r] = M * f16(x[r]) for the first ``rows`` rows, ONE pass over the matrix;
@@ -652,8 +653,10 @@ class Decoder:
         effort_bucket_gemm_rows_routed): no core is read, and there is no fallback -- every refusal of the library was ruled out by
         ``prefill`` before anything was enqueued, so one is an error.  ``q4`` (``weights="q4"``, dense FFN only) decides per bundle:
         a Q4 bundle multiplies by ``unbucket_q4()`` of its buckets plus its outliers (effort_q4_gemm_rows, expert 0; no core is
-        read, no fallback), a core-only bundle goes the way of the cores."""
+        read, no fallback), a core-only bundle goes the way of the cores.  ``wide`` (cores, dense FFN only): ``mul`` is
+        effort_dense_gemm_rows_wide, up to 256 rows a call and per row the same bits; the same fallback."""
         g, lib = self.g, _lib.lib()
+        gemm_rows = lib.effort_dense_gemm_rows_wide if wide else lib.effort_dense_gemm_rows
         if from_buckets:
             def mul(x, ew, out, rows):
                 g.check(lib.effort_bucket_gemm_rows(g.ctx, ew.handle, 0, _p(x), _p(out), rows), "bucket_gemm_rows")
@@ -664,7 +667,7 @@ class Decoder:
 
         def mul(x, ew, out, rows):
             core = ew.core
-            rc = lib.effort_dense_gemm_rows(g.ctx, _p(core), _p(x), _p(out), int(core.shape[1]), int(core.shape[0]), rows)
+            rc = gemm_rows(g.ctx, _p(core), _p(x), _p(out), int(core.shape[1]), int(core.shape[0]), rows)
             if rc == -2:
                 for r in range(rows):
                     basicMul(x[r], core, out[r])
@@ -692,7 +695,7 @@ class Decoder:
         return mul, mul_routed
 
     def prefill(self, tokenIds: list[int], pos0: int = 0, chunk: int = 64, attention: str = "rows", ffn: str = "dense",
-                weights: str = "cores"):
+                weights: str = "cores", wide: bool = False):
         """Ingest prompt tokens in bulk: fill ``kCache`` / ``vCache`` rows ``pos0 .. pos0 + T - 1`` of every layer, in blocks of at most
         ``chunk`` (<= 64) tokens that share ONE pass over each matrix, then set ``pos`` to ``pos0 + T``.  No logits, no pick: the next
         ``token_step`` (or graph replay) continues from the caches.  Eager, never captured: ``pos0`` and the block sizes are host values.
@@ -739,12 +742,21 @@ class Decoder:
         its core by the whole quantisation.  Every Q4 handle is asked once whether it is un-bucketable
         (effort_weights_q4_dense_ok).  Dense FFN only.
 
+        ``wide``: ``chunk`` may be 1 .. 256, and the seven multiplies of a layer go through effort_dense_gemm_rows_wide on the whole
+        block -- a quarter of the passes over the weights at 256.  The per-row glue, the cache writer and the attention keep their 64-row
+        limit: they are called on consecutive sub-blocks of at most 64 rows of the block's buffers, ``pos0`` advanced per sub-block,
+        each sub-block's cache write before its attention.  A wide product's row has the 64-row kernel's bits and the glue's and the
+        attention's bits follow the absolute position alone, so the caches and rings are those of ``wide=False`` at any ``chunk``.
+        Serves ``weights="cores"`` with ``ffn="dense"``, every cache kind and every ``attention``.  Opt-in: the default is as before,
+        call for call.
+
         Raises ValueError, before anything is enqueued: a ``weights`` other than ``"cores"`` / ``"buckets"`` / ``"q4"``; under ``"q4"``
         an FP16 bucketed bundle (``"buckets"`` is its path), a core-only bundle without its core, a Q4 bundle that is not
         un-bucketable and ``ffn="routed"``; under ``"buckets"`` a Q4
         or core-only bundle, a bundle truncated below ``percentLoad`` 16 and one that is not un-bucketable; a bundle without its core (FP16 models need ``keep_cores``; Q4 models keep
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
-        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"`` /
+        ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64 (``wide``: 1 .. 256), ``wide`` with ``weights`` other than ``"cores"`` or
+        with ``ffn="routed"``, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"`` /
         ``"flash_window"``, ``"flash"`` on an f32-cache or a ``window`` decoder, ``"flash_window"`` on any decoder but a
         ``kv_cache="f16", window=W`` one, an ``ffn`` other than ``"dense"`` / ``"routed"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
@@ -755,6 +767,10 @@ class Decoder:
         if weights not in ("cores", "buckets", "q4"):
             raise ValueError(f"Decoder.prefill: weights must be 'cores' or 'buckets', not {weights!r} (or 'q4', for a model with Q4 bundles)")
         routed, from_buckets, from_q4 = ffn == "routed", weights == "buckets", weights == "q4"
+        if wide and (from_buckets or from_q4 or routed):
+            raise ValueError("Decoder.prefill: wide=True serves weights='cores' with ffn='dense' alone (the bucket, Q4 and routed block multiplies stop at 64 rows)")
+        if wide and self.sharded:
+            raise ValueError("Decoder.prefill: wide=True is not implemented for the column-sharded decode loop")
         if from_q4 and routed:
             raise ValueError("Decoder.prefill: weights='q4' serves ffn='dense' alone (the reference writes no Q4 Mixtral model)")
         if routed and not (cfg.numExperts >= 2 and all(L.ffnGate is not None and L.ffnGate.dtype == torch.float16 for L in m.layers)):
@@ -780,8 +796,9 @@ class Decoder:
             raise ValueError("Decoder.prefill: every bundle needs its f16 core (Model.random(keep_cores=True), or a Q4 model)")
         if routed and not from_buckets and any(getattr(L, w).core.dim() != 3 or int(getattr(L, w).core.shape[0]) != cfg.numExperts for L in m.layers for w in ("w1", "w2", "w3")):
             raise ValueError("Decoder.prefill: ffn='routed' needs the expert stacks' cores [numExperts, out, in] (Model.random(keep_cores=True))")
-        if not 1 <= chunk <= self.PREFILL_MAX_ROWS:
-            raise ValueError(f"Decoder.prefill: chunk must be 1 .. {self.PREFILL_MAX_ROWS}")
+        maxChunk = self.PREFILL_WIDE_MAX_ROWS if wide else self.PREFILL_MAX_ROWS
+        if not 1 <= chunk <= maxChunk:
+            raise ValueError(f"Decoder.prefill: chunk must be 1 .. {maxChunk}" + ("" if wide else " (wide=True: 1 .. 256)"))
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
         if attention not in ("rows", "block", "flash", "flash_window"):
@@ -829,24 +846,36 @@ class Decoder:
         self._prefill_buffers(chunk)
         ck = lambda rc, what: g.check(rc, what)                                     # noqa: E731
         rope = C.c_float(cfg.ropeBase)
-        mul, mul_routed = self._block_multiplies(from_buckets, from_q4)
+        mul, mul_routed = self._block_multiplies(from_buckets, from_q4, wide)
+        # The glue's, the cache writer's and the attention's row limit: a wide block goes through them in sub-blocks (r0, n) of at most 64
+        # rows -- views of the block buffers from row r0 on, the position advanced by r0.  Without ``wide`` a block is its one sub-block.
+        sub = lambda rows: [(r0, min(self.PREFILL_MAX_ROWS, rows - r0)) for r0 in range(0, rows, self.PREFILL_MAX_ROWS)]   # noqa: E731
+        at = lambda t, r0: None if t is None else _p(t[r0:] if r0 else t)           # noqa: E731
         for b0 in range(0, T, chunk):
             rows, p = min(chunk, T - b0), pos0 + b0
             self.pf_ids[:rows].copy_(torch.tensor(ids[b0:b0 + rows], dtype=torch.int32))
-            ck(lib.effort_fetch_rows(g.ctx, _p(m.tokEmbeddings), _p(self.pf_ids), _p(self.pf_h), cfg.stateDim, rows), "fetch_rows")
+            for r0, nr in sub(rows):
+                ck(lib.effort_fetch_rows(g.ctx, _p(m.tokEmbeddings), at(self.pf_ids, r0), at(self.pf_h, r0), cfg.stateDim, nr), "fetch_rows")
             delta = None                                   # a product not yet added to h, exactly as in token_step
             for n, L in enumerate(m.layers):
                 kc, vc = _p(self.kCache[n]), _p(self.vCache[n])
-                ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(delta), _p(L.attnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
+                for r0, nr in sub(rows):
+                    ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, at(self.pf_h, r0), at(delta, r0), _p(L.attnNorm), at(self.pf_norm, r0), cfg.stateDim, nr), "rmsnorm_rows")
                 for ew, out in ((L.wq, self.pf_xq_temp), (L.wk, self.pf_xk_temp), (L.wv, self.pf_xv_temp)):
                     mul(self.pf_norm, ew, out, rows)
-                ck(rope_rows(g.ctx, _p(self.pf_xq_temp), _p(self.pf_xk_temp), _p(self.pf_xv_temp), _p(self.pf_xq), kc, vc, p, rows,
-                             cfg.numHeads, cfg.numHeadsKV, cfg.headDim, *cacheArgs, rope), "rope_kv_rows")
-                if n == len(m.layers) - 1:
+                last = n == len(m.layers) - 1
+                for r0, nr in sub(rows):                   # (each sub-block's cache write before its attention: a ring's rows are its own by then)
+                    ck(rope_rows(g.ctx, at(self.pf_xq_temp, r0), at(self.pf_xk_temp, r0), at(self.pf_xv_temp, r0), at(self.pf_xq, r0), kc, vc, p + r0, nr,
+                                 cfg.numHeads, cfg.numHeadsKV, cfg.headDim, *cacheArgs, rope), "rope_kv_rows")
+                    if not last:
+                        ck(attend(g.ctx, at(self.pf_xq, r0), kc, vc, p + r0, nr, at(self.pf_attnOutput, r0), cfg.numHeads, *kvh, cfg.headDim, *cacheArgs,
+                                  *windowArgs), attendName)
+                if last:
                     break                                  # nothing after the last layer's cache write reaches a cache
-                ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, *kvh, cfg.headDim, *cacheArgs, *windowArgs), attendName)
                 mul(self.pf_attnOutput, L.wo, self.pf_attnFfnOut, rows)
-                ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, _p(self.pf_h), _p(self.pf_attnFfnOut), _p(L.ffnNorm), _p(self.pf_norm), cfg.stateDim, rows), "rmsnorm_rows")
+                for r0, nr in sub(rows):
+                    ck(lib.effort_add_rmsnorm_mul_rows(g.ctx, at(self.pf_h, r0), at(self.pf_attnFfnOut, r0), _p(L.ffnNorm), at(self.pf_norm, r0), cfg.stateDim, nr),
+                       "rmsnorm_rows")
                 if routed:
                     idx2 = self.pf_gateIdxs[n]
                     ck(lib.effort_moe_route_rows(g.ctx, _p(self.pf_h), _p(L.ffnNorm), _p(L.ffnGate), cfg.stateDim, cfg.numExperts, _p(self.pf_gateOut[n]),
@@ -906,7 +935,8 @@ class Decoder:
 
     def run(self, tokenIds: list[int], numTokens: int, effort: float = 0.25, dense: bool = False, forced: bool = False,
             collect_logits: bool = False, sampling=None, prefill: bool = False, prefill_chunk: int = 64,
-            prefill_attention: str = "rows", prefill_ffn: str = "dense", prefill_weights: str = "cores", rules=None, stop_poll: int = 16):
+            prefill_attention: str = "rows", prefill_ffn: str = "dense", prefill_weights: str = "cores", rules=None, stop_poll: int = 16,
+            prefill_wide: bool = False):
         """runNetwork(tokens:effort:): feed the prompt one token per step, then continue greedily until ``numTokens``
         steps have run.  ``forced``: every step's input comes from ``tokenIds`` (teacher forcing, for the KL measurement).
         ``sampling``: a ``Sampling`` -- every step's pick is the device-side draw (temperature / top-k / top-p, Philox at counter
@@ -919,7 +949,7 @@ class Decoder:
         ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"`` / ``"flash_window"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
         ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
         FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
-        and the caches then hold effort-1.0 K / V, not dense ones).
+        and the caches then hold effort-1.0 K / V, not dense ones), ``prefill_wide`` its ``wide`` (``prefill_chunk`` up to 256, the same caches).
         ``rules``: a ``Rules`` -- every step applies the generation rules on the device (effort_logit_rules between the LM head and the
         pick: penalties over the last ``last_n`` tokens fed, the logit bias, min-p), the step graph is shared by every setting, and
         ``collect_logits`` still returns the RAW logits.  The prompt never stops a run (``first_pos = len(tokenIds)``); prefilled prompt ids
@@ -957,7 +987,7 @@ class Decoder:
         if skip:
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn, prefill_weights)
+            self.prefill(tokenIds[:skip], 0, prefill_chunk, prefill_attention, prefill_ffn, prefill_weights, **({"wide": True} if prefill_wide else {}))
             torch.cuda.synchronize()
             self.last_prefill_s = time.perf_counter() - tp
             if rules is not None:

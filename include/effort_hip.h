@@ -463,6 +463,18 @@ EFFORT_API int effort_decode_status(effort_ctx* ctx, int* host_out);
  * either buffer: before capturing, call it eagerly with 64 rows once for EVERY (inDim, outDim) pair the context will ever see.
  * Up to three launches: convert, multiply, and the reduce when the shape has more than one split. */
 EFFORT_API int effort_dense_gemm_rows(effort_ctx* ctx, const void* W_f16_dev, const float* x_dev, float* out_dev, int inDim, int outDim, int rows);
+/* The WIDE block multiply: effort_dense_gemm_rows for 1 .. EFFORT_PREFILL_WIDE_MAX_ROWS rows in ONE pass over W (csrc/prefill_wide.hip: a
+ * tiling of its own, a wave on two 16-row tiles of W and up to eight token tiles).  Operands and shapes are effort_dense_gemm_rows's.
+ * CONTRACT: row r of out is BIT FOR BIT what effort_dense_gemm_rows writes for that row of x (the same k split, the same order of the
+ * sums, the same operand slots, zero operands for dead token columns and for k past inDim); so that entry's contract holds here word
+ * for word -- no x row at or beyond rows is read, nothing at or beyond rows * outDim is written.  The weight stream is nt when W is above
+ * 64 MiB.  Refusals in that entry's order, nothing enqueued on any: rows outside 1 .. 256 or a dimension < 1: EFFORT_ERR_ARG; a shape
+ * it refuses: EFFORT_ERR_SHAPE; then a null pointer: EFFORT_ERR_ARG.
+ * SCRATCH of its OWN (a captured effort_dense_gemm_rows keeps that entry's addresses): 256 * inDim halves and splits * 256 * outDim
+ * floats, allocated by the first call of THIS entry point -- a context that never calls it holds none -- and grown by that entry's
+ * rule.  Up to three launches.  Every other prefill entry point keeps its 64-row limit. */
+#define EFFORT_PREFILL_WIDE_MAX_ROWS 256
+EFFORT_API int effort_dense_gemm_rows_wide(effort_ctx* ctx, const void* W_f16_dev, const float* x_dev, float* out_dev, int inDim, int outDim, int rows);
 /* The ROUTED block multiply (a Mixtral block): W f16 [numExperts][outDim][inDim], one expert's matrix as effort_dense_gemm_rows takes it.
  * Assignment a = 2 r + s (token r < rows, slot s of its top-2) multiplies expert e = min(idx2_dev[a], numExperts - 1) -- the clamp of
  * effort_dense_gemv_expert: a device value cannot be refused by a return code.  Its input row is x[r] when xPerSlot == 0 (w1 / w3: both

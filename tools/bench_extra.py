@@ -32,7 +32,9 @@ f16 MFMA, effort_attention_flash_f16, beside effort_attention_block_f16 at posit
 both ways; its record also goes to profiles/r19_attention_flash16.json; standalone too) and `prefill_attention_flash_window` (its
 ring form, effort_attention_flash_window, beside effort_attention_block_window at window 4096 and positions 960 .. 32704, with
 effort_attention_flash_f16 over the same 4096 keys as the yardstick, and `Decoder.prefill` over 2048 tokens on a window=4096 decoder
-both ways; its record also goes to profiles/r20_attention_flash_window.json; standalone too).
+both ways; its record also goes to profiles/r20_attention_flash_window.json; standalone too) and `prefill_wide` (the wide block
+multiply, effort_dense_gemm_rows_wide at 128, 192 and 256 rows, beside the 64-row calls it replaces, and `Decoder.prefill` over 2048
+tokens at chunk 64 and with wide=True at chunk 128 and 256; its record also goes to profiles/r21_prefill_wide.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -51,9 +53,9 @@ import bench as B  # noqa: E402
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
             "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-            "prefill_attention_flash", "prefill_attention_flash_window")
+            "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide")
 STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-              "prefill_attention_flash", "prefill_attention_flash_window")   # sections that read neither the headline nor the matrix sets of bench.Bench
+              "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide")   # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1596,6 +1598,83 @@ def prefill_attention_flash_window(b, res):
     del dec, model
 
 
+def prefill_wide(b, res):
+    """Wide prefill blocks: effort_dense_gemm_rows_wide beside the 64-row calls it replaces, one process, the legs' windows alternating.
+    Kernel legs, decode_prefill's protocol (rotating disjoint matrices, more than 768 MB of them per shape): on the decode loop's four
+    matrix shapes, N calls of effort_dense_gemm_rows at 64 rows (old), ONE wide call at 64 N rows (new) and the old leg again (its
+    run-to-run spread), N = 2, 3, 4; and the wide call at 64 rows beside the 64-row call.  us per pass over one matrix's tokens.  Model
+    legs, Mistral-7B shapes, a 2048-token prompt on a kv_cache="f16" decoder with attention="flash": chunk 64, wide at chunk 128 and 256,
+    chunk 64 again; ms per prompt token."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t: C.c_void_p(t.data_ptr())                                       # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(121)
+    kern = {"protocol": "one pass over the rotating matrices per graph, 4 replays per window, best of 3 windows, device events, the legs' windows "
+                        "alternating; old = N calls of effort_dense_gemm_rows at 64 rows, wide = one effort_dense_gemm_rows_wide at 64 N rows, "
+                        "old_again = old captured a second time: its difference from old is the spread; us per matrix"}
+    for outD, inD in ((4096, 4096), (14336, 4096), (4096, 14336), (1024, 4096)):
+        nbytes = outD * inD * 2
+        count = max(4, -(-(768 << 20) // nbytes))
+        Ws = [(torch.randn((outD, inD), generator=gen, device=b.dev, dtype=torch.float32) * 0.02).to(torch.float16) for _ in range(count)]
+        x = torch.randn((256, inD), generator=gen, device=b.dev, dtype=torch.float32)
+        outs = {name: torch.zeros((256, outD), device=b.dev) for name in ("old", "wide")}
+
+        def old(n):
+            def fn():
+                g._bind_stream()
+                for W in Ws:
+                    for i in range(n):
+                        g.check(lib.effort_dense_gemm_rows(g.ctx, p(W), p(x[64 * i:]), p(outs["old"][64 * i:]), inD, outD, 64), "dense_gemm_rows")
+            return fn
+
+        def wide(rows):
+            def fn():
+                g._bind_stream()
+                for W in Ws:
+                    g.check(lib.effort_dense_gemm_rows_wide(g.ctx, p(W), p(x), p(outs["wide"]), inD, outD, rows), "dense_gemm_rows_wide")
+            return fn
+        row = {"matrices": count, "weight_bytes": nbytes}
+        for n in (1, 2, 3, 4):
+            us = alternating_us(b, {"old": old(n), "wide": wide(64 * n), "old_again": old(n)}, count)
+            torch.cuda.synchronize()
+            row[f"rows_{64 * n}"] = dict({name + "_us": round(t, 2) for name, t in us.items()}, old_over_wide_time=round(us["old"] / us["wide"], 3),
+                                         old_again_over_old=round(us["old_again"] / us["old"], 3),
+                                         same_bits=bool(torch.equal(outs["old"][:64 * n].view(torch.int32), outs["wide"][:64 * n].view(torch.int32))))
+            B.log(f"prefill_wide: {inD}->{outD} rows {64 * n}: {row[f'rows_{64 * n}']}")
+        kern[f"{inD}->{outD}"] = row
+        del Ws, x, outs
+        torch.cuda.empty_cache()
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    nprompt = 2048
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "kv_cache": "f16", "attention": "flash", "prompt": nprompt,
+         "protocol": "eager, synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call; chunk 64 twice, around the wide legs"}
+    dec = Decoder(model, maxTokens=nprompt + 8, kv_cache="f16")
+    prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+    for key, kw in (("chunk_64", dict(chunk=64)), ("wide_chunk_128", dict(chunk=128, wide=True)), ("wide_chunk_256", dict(chunk=256, wide=True)),
+                    ("chunk_64_again", dict(chunk=64))):
+        m[key + "_ms_per_prompt_token"] = timed_prefill(b, dec, prompt, attention="flash", **kw)
+        B.log(f"prefill_wide: model {key}: {m[key + '_ms_per_prompt_token']} ms per prompt token")
+    for key in ("wide_chunk_128", "wide_chunk_256", "chunk_64_again"):
+        m[f"chunk_64_over_{key}"] = round(m["chunk_64_ms_per_prompt_token"] / m[key + "_ms_per_prompt_token"], 3)
+    res_out["model"] = m
+    res["prefill_wide"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r21_prefill_wide.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del dec, model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1615,7 +1694,7 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
        "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
        "decode_window": decode_window, "decode_kv16_short": decode_kv16_short, "prefill_attention_flash": prefill_attention_flash,
-       "prefill_attention_flash_window": prefill_attention_flash_window}
+       "prefill_attention_flash_window": prefill_attention_flash_window, "prefill_wide": prefill_wide}
 
 
 class Light:

@@ -299,6 +299,10 @@ hipError_t launch_attention_block_f16(const float* q, const _Float16* kCache, co
 // (attention_flash16.hip: 32-key tiles, V transposed through LDS; the f32 bar, other bits)
 hipError_t launch_attention_flash_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
                                       uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
+// ... and the same bits for a block of up to 256 queries, the query heads of a GQA group sharing each K / V tile
+// (attention_flash_group.hip: a workgroup is one KV head, 16 queries and min(R, 512 / headDim) of the group's heads)
+hipError_t launch_attention_flash_group_f16(const float* q, const _Float16* kCache, const _Float16* vCache, uint32_t pos0, uint32_t rows, float* out,
+                                            uint32_t numHeads, uint32_t numHeadsKV, uint32_t headDim, hipStream_t st);
 // ... and its one-launch token step for short contexts (kv16_short.hip): rope, the write of row *pos and the attention over rows
 // 0 .. *pos < maxKeys, one workgroup per query head, the scores in maxKeys floats of dynamic LDS
 constexpr int kShortMaxKeys = 2048;

@@ -491,6 +491,17 @@ extern "C" int effort_attention_flash_f16(effort_ctx* c, const float* q, const v
     return HIP_RC(c, launch_attention_flash_f16(q, static_cast<const _Float16*>(kCache), static_cast<const _Float16*>(vCache), (uint32_t)pos0, (uint32_t)rows, out,
                                                 (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, c->stream));
 }
+// ... its bits for a block of up to EFFORT_ATTENTION_GROUP_MAX_ROWS rows, a GQA group's heads sharing the K / V tiles: the same refusals
+extern "C" int effort_attention_flash_group_f16(effort_ctx* c, const float* q, const void* kCache, const void* vCache, int pos0, int rows, float* out,
+                                                int numHeads, int numHeadsKV, int headDim, int maxTokens) {
+    if (rows < 1 || rows > EFFORT_ATTENTION_GROUP_MAX_ROWS || pos0 < 0 || maxTokens <= 0 || pos0 > maxTokens - rows)
+        return kv16_refuse(c, "attention_flash_group_f16", EFFORT_ERR_ARG, "1 <= rows <= 256, 0 <= pos0, pos0 + rows <= maxTokens");
+    if (!kv16_shape_ok(numHeads, numHeadsKV, headDim, maxTokens)) return kv16_refuse(c, "attention_flash_group_f16", EFFORT_ERR_SHAPE, kKv16Shape);
+    if (!c || !q || !kCache || !vCache || !out) return kv16_refuse(c, "attention_flash_group_f16", EFFORT_ERR_ARG, "null argument");
+    JOIN_TRY(c);
+    return HIP_RC(c, launch_attention_flash_group_f16(q, static_cast<const _Float16*>(kCache), static_cast<const _Float16*>(vCache), (uint32_t)pos0, (uint32_t)rows,
+                                                      out, (uint32_t)numHeads, (uint32_t)numHeadsKV, (uint32_t)headDim, c->stream));
+}
 // ... and the block forms on the rolling cache: rows and pos0 first (the range of positions is part of the shape), then the shape
 extern "C" int effort_rope_kv_rows_ring(effort_ctx* c, const float* xq, const float* xk, const float* xv, float* qOut, void* kRing, void* vRing,
                                         int pos0, int rows, int numHeads, int numHeadsKV, int headDim, int ringRows, float ropeBase) {

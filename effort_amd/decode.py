@@ -197,7 +197,7 @@ class Decoder:
     it serves, and everything above applies.  ``"f16"`` -- the compact caches, torch.float16 [maxTokens][numHeadsKV][headDim] (csrc/kv16.hip):
     1 / (2 R) of the memory, R = numHeads / numHeadsKV, and maxTokens up to 32768.  EVERY token step's attention is then
     effort_rope_kv_f16 + effort_attention_split_f16 (one captured step per effort, whatever ``fused_attention`` and the folded glue say)
-    and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"``; ``"flash"``: effort_attention_flash_f16).  Any model kind; K and V are
+    and ``prefill`` runs effort_rope_kv_rows_f16 + effort_attention_block_f16 (``attention="block"``; ``"flash"``: effort_attention_flash_f16; ``"flash_group"``: effort_attention_flash_group_f16).  Any model kind; K and V are
     rounded to f16 on their way into the cache, nothing upstream of the rope changes.  Needs R in 1, 2, 4, 8 and headDim 64 / 128 / 256;
     not with a column-sharded decoder, and not with ``split_attention_from`` (the split is implied).
 
@@ -714,6 +714,9 @@ class Decoder:
         effort_rope_kv_rows_f16 + effort_attention_block_f16, or -- without a ``window`` -- ``"flash"``, which puts
         effort_attention_flash_f16 in the attention's place: both products on the f16 MFMA, q and the probabilities split into two
         halves each, the same f32 bar, other bits, the caches again independent of ``chunk``.  Opt-in: nothing selects it by default.
+        ``"flash_group"``, on the same decoders, is effort_attention_flash_group_f16: ``"flash"``'s bits with the query heads of a GQA
+        group sharing each K / V tile and blocks of up to 256 rows, so the caches and the next step's logits are ``"flash"``'s at any
+        ``chunk``.  Opt-in as well.
         A ``kv_cache="f16", window=W`` decoder takes ``"block"`` (effort_attention_block_window) or ``"flash_window"``, the ring form of
         ``"flash"``: effort_attention_flash_window in the attention's place, same writer, same arguments; its bits are ``"flash"``'s
         while the block ends at or below position W, and the rings do not depend on ``chunk``.  Opt-in as well; ``"flash"`` itself stays
@@ -747,6 +750,8 @@ class Decoder:
         limit: they are called on consecutive sub-blocks of at most 64 rows of the block's buffers, ``pos0`` advanced per sub-block,
         each sub-block's cache write before its attention.  A wide product's row has the 64-row kernel's bits and the glue's and the
         attention's bits follow the absolute position alone, so the caches and rings are those of ``wide=False`` at any ``chunk``.
+        Under ``attention="flash_group"`` the cache writer still runs per sub-block and the attention is ONE call on the whole block,
+        after the block's last cache write.
         Serves ``weights="cores"`` with ``ffn="dense"``, every cache kind and every ``attention``.  Opt-in: the default is as before,
         call for call.
 
@@ -757,7 +762,7 @@ class Decoder:
         them), a Mixtral model under ``ffn="dense"`` and a dense-FFN model under ``ffn="routed"``, a column-sharded decoder,
         ``pos0 + T > maxTokens``, ``chunk`` outside 1 .. 64 (``wide``: 1 .. 256), ``wide`` with ``weights`` other than ``"cores"`` or
         with ``ffn="routed"``, an ``attention`` other than ``"rows"`` / ``"block"`` / ``"flash"`` /
-        ``"flash_window"``, ``"flash"`` on an f32-cache or a ``window`` decoder, ``"flash_window"`` on any decoder but a
+        ``"flash_group"`` / ``"flash_window"``, ``"flash"`` or ``"flash_group"`` on an f32-cache or a ``window`` decoder, ``"flash_window"`` on any decoder but a
         ``kv_cache="f16", window=W`` one, an ``ffn`` other than ``"dense"`` / ``"routed"``."""
         cfg, g, lib, m = self.cfg, self.g, _lib.lib(), self.model
         ids, pos0, chunk = [int(t) for t in tokenIds], int(pos0), int(chunk)
@@ -801,11 +806,14 @@ class Decoder:
             raise ValueError(f"Decoder.prefill: chunk must be 1 .. {maxChunk}" + ("" if wide else " (wide=True: 1 .. 256)"))
         if T < 1 or pos0 < 0 or pos0 + T > self.maxTokens:
             raise ValueError(f"Decoder.prefill: tokens {pos0} .. {pos0 + T - 1} do not fit maxTokens = {self.maxTokens}")
-        if attention not in ("rows", "block", "flash", "flash_window"):
-            raise ValueError(f"Decoder.prefill: attention must be 'rows', 'block', 'flash' or 'flash_window', not {attention!r}")
+        if attention not in ("rows", "block", "flash", "flash_group", "flash_window"):
+            raise ValueError(f"Decoder.prefill: attention must be 'rows', 'block', 'flash', 'flash_group' or 'flash_window', not {attention!r}")
         if attention == "flash" and (not self.kv16 or self.window is not None):
             raise ValueError("Decoder.prefill: attention must be " + ("'block'" if self.kv16 else "'rows' or 'block'") + " on this decoder: 'flash' is "
                              "for kv_cache='f16' without a window (effort_attention_flash_f16 reads the compact f16 cache; its ring form is 'flash_window')")
+        if attention == "flash_group" and (not self.kv16 or self.window is not None):
+            raise ValueError("Decoder.prefill: attention must be " + ("'block'" if self.kv16 else "'rows' or 'block'") + " on this decoder: 'flash_group' "
+                             "is for kv_cache='f16' without a window (effort_attention_flash_group_f16 reads the compact f16 cache)")
         if attention == "flash_window" and self.window is None:
             raise ValueError("Decoder.prefill: attention must be " + ("'block' or 'flash'" if self.kv16 else "'rows' or 'block'") + " on this decoder: "
                              "'flash_window' is for kv_cache='f16' with a window (effort_attention_flash_window reads the rolling f16 cache)")
@@ -821,6 +829,7 @@ class Decoder:
         elif self.kv16:
             rope_rows = lib.effort_rope_kv_rows_f16
             attend, attendName = ((lib.effort_attention_flash_f16, "attention_flash_f16") if attention == "flash" else
+                                  (lib.effort_attention_flash_group_f16, "attention_flash_group_f16") if attention == "flash_group" else
                                   (lib.effort_attention_block_f16, "attention_block_f16"))
         else:
             rope_rows = lib.effort_rope_kv_rows
@@ -849,6 +858,11 @@ class Decoder:
         mul, mul_routed = self._block_multiplies(from_buckets, from_q4, wide)
         # The glue's, the cache writer's and the attention's row limit: a wide block goes through them in sub-blocks (r0, n) of at most 64
         # rows -- views of the block buffers from row r0 on, the position advanced by r0.  Without ``wide`` a block is its one sub-block.
+        # The one exception is attention="flash_group", whose entry point takes 256 rows: the cache writer still runs per sub-block and
+        # the attention is ONE call on the whole block after the block's last cache write.  The plain cache makes this legal -- a query
+        # reads only rows at or below its own position, and no write of the block lands on a row another of its queries still needs (on
+        # a ring it could) -- and by that entry point's bit guarantee the output is that of the per-sub-block "flash" calls.
+        whole = attention == "flash_group"
         sub = lambda rows: [(r0, min(self.PREFILL_MAX_ROWS, rows - r0)) for r0 in range(0, rows, self.PREFILL_MAX_ROWS)]   # noqa: E731
         at = lambda t, r0: None if t is None else _p(t[r0:] if r0 else t)           # noqa: E731
         for b0 in range(0, T, chunk):
@@ -867,9 +881,11 @@ class Decoder:
                 for r0, nr in sub(rows):                   # (each sub-block's cache write before its attention: a ring's rows are its own by then)
                     ck(rope_rows(g.ctx, at(self.pf_xq_temp, r0), at(self.pf_xk_temp, r0), at(self.pf_xv_temp, r0), at(self.pf_xq, r0), kc, vc, p + r0, nr,
                                  cfg.numHeads, cfg.numHeadsKV, cfg.headDim, *cacheArgs, rope), "rope_kv_rows")
-                    if not last:
+                    if not last and not whole:
                         ck(attend(g.ctx, at(self.pf_xq, r0), kc, vc, p + r0, nr, at(self.pf_attnOutput, r0), cfg.numHeads, *kvh, cfg.headDim, *cacheArgs,
                                   *windowArgs), attendName)
+                if not last and whole:
+                    ck(attend(g.ctx, _p(self.pf_xq), kc, vc, p, rows, _p(self.pf_attnOutput), cfg.numHeads, *kvh, cfg.headDim, *cacheArgs), attendName)
                 if last:
                     break                                  # nothing after the last layer's cache write reaches a cache
                 mul(self.pf_attnOutput, L.wo, self.pf_attnFfnOut, rows)
@@ -946,7 +962,7 @@ class Decoder:
         and every later step are the ordinary captured step at the requested ``effort`` / ``dense`` / ``sampling``.  No pick exists
         for the prefilled positions: the returned list has -1 there, ``collect_logits`` starts at step P - 1, and ``last_prefill_s``
         holds the synchronised wall time of the prefill.  Not with ``forced``.  The default is the token-by-token loop.
-        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"`` / ``"flash_window"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
+        ``prefill_attention`` is ``prefill``'s ``attention`` (``"rows"`` / ``"block"`` / ``"flash"`` / ``"flash_group"`` / ``"flash_window"``), ``prefill_ffn`` its ``ffn`` (``"dense"`` /
         ``"routed"``: a Mixtral prompt prefills only with ``"routed"``), ``prefill_weights`` its ``weights`` (``"cores"`` / ``"buckets"`` / ``"q4"``: an
         FP16 model without cores prefills only with ``"buckets"``, a Q4 model without the cores of its Q4 bundles only with ``"q4"``,
         and the caches then hold effort-1.0 K / V, not dense ones), ``prefill_wide`` its ``wide`` (``prefill_chunk`` up to 256, the same caches).

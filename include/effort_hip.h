@@ -628,6 +628,23 @@ EFFORT_API int effort_attention_block_f16(effort_ctx* ctx, const float* q_dev, c
  *   pos0 + rows and no q row at or past rows is read; nothing outside out[0 .. rows) is written. */
 EFFORT_API int effort_attention_flash_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev, int pos0,
                                int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
+/* effort_attention_flash_group_f16: effort_attention_flash_f16's operands, layouts and arithmetic for a block of 1 ..
+ *   EFFORT_ATTENTION_GROUP_MAX_ROWS rows, with the query heads of a GQA group sharing each K / V tile.  A workgroup is one KV head, 16
+ *   query positions and HPW = min(R, 512 / headDim) of that group's query heads (R = numHeads / numHeadsKV; the R / HPW head groups
+ *   are part of the grid): the wave that owns a 32-key tile loads its K fragments, stages and transposes its V tile and computes the
+ *   causal mask ONCE and uses them for all HPW heads, each with its own softmax state and accumulator.  At 32 / 8 heads, headDim 128,
+ *   a block asks for every K / V byte a quarter as often as effort_attention_flash_f16 does.  Guarantees:
+ *   - output row r, head h has BIT FOR BIT the bits effort_attention_flash_f16 writes for the same q row, position and cache (per head
+ *     the order of every sum, the tile-to-wave map and the merge order are unchanged; only where operands come from differs), so a
+ *     block of up to 256 rows equals that entry point called on slices of at most 64 rows;
+ *   - hence an output row's bits are a function of the query, its absolute position pos0 + r and cache rows 0 .. pos0 + r alone;
+ *   - no cache row at or past pos0 + rows and no q row at or past rows is read; nothing outside out[0 .. rows) is written;
+ *   - no scratch segment and no spills at headDim 64 / 128 / 256 and R 1 / 2 / 4 / 8.
+ * Refusals in effort_attention_flash_f16's order: rows outside 1 .. 256, pos0 < 0, pos0 + rows > maxTokens EFFORT_ERR_ARG; the shape
+ * EFFORT_ERR_SHAPE; a null pointer EFFORT_ERR_ARG. */
+#define EFFORT_ATTENTION_GROUP_MAX_ROWS 256
+EFFORT_API int effort_attention_flash_group_f16(effort_ctx* ctx, const float* q_dev, const void* k_cache_f16_dev, const void* v_cache_f16_dev,
+                                     int pos0, int rows, float* out_dev, int numHeads, int numHeadsKV, int headDim, int maxTokens);
 /* The block forms on the rolling cache (see effort_rope_kv_ring for the format and the shapes).
  * effort_rope_kv_rows_ring: effort_rope_kv_rows_f16 with token pos0 + r in ring row (pos0 + r) % ringRows: per row its bits, q_out
  *   included; those `rows` ring rows are written, no other.  rows <= ringRows.

@@ -34,7 +34,11 @@ ring form, effort_attention_flash_window, beside effort_attention_block_window a
 effort_attention_flash_f16 over the same 4096 keys as the yardstick, and `Decoder.prefill` over 2048 tokens on a window=4096 decoder
 both ways; its record also goes to profiles/r20_attention_flash_window.json; standalone too) and `prefill_wide` (the wide block
 multiply, effort_dense_gemm_rows_wide at 128, 192 and 256 rows, beside the 64-row calls it replaces, and `Decoder.prefill` over 2048
-tokens at chunk 64 and with wide=True at chunk 128 and 256; its record also goes to profiles/r21_prefill_wide.json; standalone too).
+tokens at chunk 64 and with wide=True at chunk 128 and 256; its record also goes to profiles/r21_prefill_wide.json; standalone too) and
+`prefill_attention_flash_group` (the f16-MFMA block attention with a GQA group's heads sharing each K / V tile,
+effort_attention_flash_group_f16 in one call of 64, 128 and 256 rows, beside effort_attention_flash_f16 in 64-row slices at positions
+0 .. 32512, and `Decoder.prefill(chunk=256, wide=True)` over 2048 and 8192 tokens both ways; its record also goes to
+profiles/r22_attention_flash_group.json; standalone too).
 
     python tools/bench_extra.py [--sections a,b,...] [--steps 20 --warmup 5 ...bench.py's flags]
 
@@ -53,9 +57,9 @@ import bench as B  # noqa: E402
 SECTIONS = ("by_streams", "shared_matrices", "four_contexts", "timeit_protocol", "heavy_tailed_input", "sweep_structured", "other_shapes",
             "shard_projection", "decode_quality", "layer_latency", "decode_q4", "decode_mixtral", "decode_sampled", "decode_prefill", "prefill_attention",
             "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-            "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide")
+            "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide", "prefill_attention_flash_group")
 STANDALONE = ("decode_prefill", "prefill_attention", "prefill_mixtral", "prefill_buckets", "prefill_q4", "decode_rules", "decode_attention_split", "decode_kv16", "decode_window", "decode_kv16_short",
-              "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide")   # sections that read neither the headline nor the matrix sets of bench.Bench
+              "prefill_attention_flash", "prefill_attention_flash_window", "prefill_wide", "prefill_attention_flash_group")   # sections that read neither the headline nor the matrix sets of bench.Bench
 
 
 def by_streams(b, res):
@@ -1675,6 +1679,89 @@ def prefill_wide(b, res):
     del dec, model
 
 
+def prefill_attention_flash_group(b, res):
+    """Prefill attention over the compact f16 cache with a GQA group's heads sharing each K / V tile: effort_attention_flash_group_f16 in
+    ONE call of 64, 128 or 256 rows beside effort_attention_flash_f16 on the same block in 64-row slices, one process, the legs' windows
+    alternating: slices / group / slices again (the two sliced legs' difference is the spread).  Kernel legs, prefill_attention_flash's
+    protocol: 32 heads, 8 KV heads, headDim 128, maxTokens 32768, eight ROTATING cache pairs per graph, device events; one more case at
+    32 / 32 heads (R = 1: nothing is shared).  Model legs, Mistral-7B shapes: `Decoder.prefill(chunk=256, wide=True)` over prompts of
+    2048 and 8192 tokens on a kv_cache="f16" decoder, flash / flash_group / flash again; ms per prompt token."""
+    import ctypes as C
+
+    import effort_amd
+    from effort_amd.decode import Decoder, MistralConfig, Model
+    torch = b.torch
+    g, lib = b.g, effort_amd.lib()
+    g.set_tuning(0, 0, 0)
+    g.set_dense_backend(False)
+    torch.cuda.empty_cache()
+    p = lambda t, r0=0: C.c_void_p(t[r0:].data_ptr())                            # noqa: E731
+    gen = torch.Generator(device=b.dev)
+    gen.manual_seed(131)
+    hd, pairs = 128, 8
+    rnd = lambda *shape: torch.randn(shape, generator=gen, device=b.dev, dtype=torch.float32)      # noqa: E731
+    kern = {"protocol": "one pass over 8 rotating f16 cache pairs per graph, 4 replays per window, best of 3 windows, device events, the legs' windows "
+                        "alternating; us per BLOCK (all its calls); slices and slices_again are the same comparator (effort_attention_flash_f16 in "
+                        "64-row slices) captured twice: their difference is the spread; bits_equal compares the last pair's outputs",
+            "headDim": hd}
+
+    def cases(nh, nkv, maxTokens, blocks):
+        caches = [(rnd(maxTokens, nkv, hd).half(), rnd(maxTokens, nkv, hd).half()) for _ in range(pairs)]
+        q, outs = rnd(256, nh * hd), {name: torch.zeros(256, nh * hd, device=b.dev) for name in ("slices", "group")}
+
+        def leg(name, pos0, rows):
+            def fn():
+                g._bind_stream()
+                for kc, vc in caches:
+                    if name == "group":
+                        g.check(lib.effort_attention_flash_group_f16(g.ctx, p(q), p(kc), p(vc), pos0, rows, p(outs[name]), nh, nkv, hd, maxTokens),
+                                "attention_flash_group_f16")
+                        continue
+                    for r0 in range(0, rows, 64):
+                        g.check(lib.effort_attention_flash_f16(g.ctx, p(q, r0), p(kc), p(vc), pos0 + r0, min(64, rows - r0), p(outs[name], r0), nh, nkv, hd,
+                                                               maxTokens), "attention_flash_f16")
+            return fn
+        for pos0, rows in blocks:
+            us = alternating_us(b, {"slices": leg("slices", pos0, rows), "group": leg("group", pos0, rows), "slices_again": leg("slices", pos0, rows)}, pairs)
+            torch.cuda.synchronize()
+            spread = abs(us["slices"] - us["slices_again"])
+            key = f"heads_{nh}_{nkv}_pos0_{pos0}_rows_{rows}"
+            kern[key] = dict({name + "_us_per_block": round(t, 2) for name, t in us.items()},
+                             slices_over_group_time=round(min(us["slices"], us["slices_again"]) / us["group"], 3),
+                             group_wins_by_more_than_twice_the_spread=bool(min(us["slices"], us["slices_again"]) - us["group"] > 2 * spread),
+                             bits_equal=bool(torch.equal(outs["group"][:rows].view(torch.int32), outs["slices"][:rows].view(torch.int32))))
+            B.log(f"prefill_attention_flash_group: {key}: {kern[key]}")
+        del caches, q, outs
+        torch.cuda.empty_cache()
+    cases(32, 8, 32768, [(pos0, rows) for pos0 in (0, 960, 4032, 8128, 32512) for rows in (64, 128, 256)])
+    cases(32, 32, 8192, [(4032, 256)])                                           # R = 1: a workgroup is one head, nothing is shared
+    res_out = {"kernel": kern}
+
+    model = Model.random(MistralConfig(), seed=1)
+    m = {"model": "Mistral-7B shapes, 32 layers, random weights, seed 1", "chunk": 256, "wide": True, "kv_cache": "f16",
+         "protocol": "eager, synchronised wall time of Decoder.prefill over the whole prompt, best of 3 after a warm call; flash twice, around flash_group"}
+    for nprompt in (2048, 8192):
+        dec = Decoder(model, maxTokens=nprompt + 8, kv_cache="f16")
+        prompt = [int(t) for t in torch.randint(0, model.cfg.vocab, (nprompt,), generator=torch.Generator().manual_seed(3))]
+        t = {}
+        for key, attention in (("flash", "flash"), ("flash_group", "flash_group"), ("flash_again", "flash")):
+            t[key] = timed_prefill(b, dec, prompt, chunk=256, wide=True, attention=attention)
+            B.log(f"prefill_attention_flash_group: model prompt {nprompt} {key}: {t[key]} ms per prompt token")
+        m[f"prompt_{nprompt}"] = dict({key + "_ms_per_prompt_token": v for key, v in t.items()},
+                                      flash_over_flash_group=round(min(t["flash"], t["flash_again"]) / t["flash_group"], 3),
+                                      group_wins_by_more_than_twice_the_spread=bool(min(t["flash"], t["flash_again"]) - t["flash_group"]
+                                                                                    > 2 * abs(t["flash"] - t["flash_again"])))
+        del dec
+        torch.cuda.empty_cache()
+    res_out["model"] = m
+    res["prefill_attention_flash_group"] = res_out
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "r22_attention_flash_group.json"), "w") as f:
+        json.dump(res_out, f, indent=1)
+        f.write("\n")
+    del model
+
+
 def layer_latency(b, res):
     """BASELINE config 4's latency case on ONE GPU: a world of one through RCCL + projected ranks."""
     b.torch.cuda.empty_cache()
@@ -1694,7 +1781,8 @@ RUN = {"by_streams": by_streams, "shared_matrices": shared_matrices, "four_conte
        "prefill_mixtral": prefill_mixtral, "prefill_buckets": prefill_buckets, "prefill_q4": prefill_q4, "decode_rules": decode_rules,
        "decode_attention_split": decode_attention_split, "decode_kv16": decode_kv16,
        "decode_window": decode_window, "decode_kv16_short": decode_kv16_short, "prefill_attention_flash": prefill_attention_flash,
-       "prefill_attention_flash_window": prefill_attention_flash_window, "prefill_wide": prefill_wide}
+       "prefill_attention_flash_window": prefill_attention_flash_window, "prefill_wide": prefill_wide,
+       "prefill_attention_flash_group": prefill_attention_flash_group}
 
 
 class Light:
